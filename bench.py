@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the MI355X ViT training step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--arch b16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--arch b16] [--dump-outputs DIR] [--full]
 
 One step = forward + cross-entropy + backward + (N>1: gradient all-reduce over RCCL) + fused
 SGD-momentum update with OneCycleLR scalars, on a synthetic batch already resident in HBM.
 Weak scaling: every rank processes --batch images (256 = BASELINE config #2 per GPU).
 For N>1 launch with torch.distributed.run (one process per GPU); rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (images/sec, ms_per_step).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
+--full adds everything that takes runs of its own: the per-kernel roofline probe steps, the committed PMC
+traffic figures, the train_epoch leg, the CPU baseline (--no-cpu-baseline / --cpu-seconds) and, for N>1, the
+gradient-exchange accounting.
 """
 from __future__ import annotations
 
@@ -177,6 +183,26 @@ def cpu_baseline(arch, image_size, num_classes, seconds_budget=20.0):
                        f"init, batch 16, {r[1]} steps in {r[2]:.1f} s; each after 1 warm-up step")
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of an output larger than this (8 MB as f32)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each named device array as out_dir/<name>.npy in float32 (float64 stays float64). An
+    array of more than DUMP_SAMPLE elements is written as a fixed sample of its flattened elements: DUMP_SAMPLE
+    sorted positions drawn once from torch.Generator().manual_seed(0), the same for every run and every build, so
+    two builds' dumps compare element for element. Five arrays at most 8 MB each stay far below 64 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.reshape(-1) if t.numel() > DUMP_SAMPLE else t
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -217,8 +243,15 @@ def main():
                     help="resvit_b16: BASELINE config C5, the Res-ViT-B/16 training step (res-vit/train.py)")
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--num-classes", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the roofline probe "
+                         "steps and committed PMC traffic, the train_epoch leg, the CPU baseline, N>1: the "
+                         "gradient-exchange accounting")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (logits, per-row loss stats, and fixed samples of "
+                         "the gradient, the updated parameters and the momentum) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: time budget of the CPU baseline")
     ap.add_argument("--grad-compress", choices=["none", "bf16"], default="none",
                     help="N>1: all-reduce the gradient buckets in bf16 (vitmi.dist compress='bf16')")
     args = ap.parse_args()
@@ -331,11 +364,96 @@ def main():
     dt = time.perf_counter() - t0
     loss_last = float(losses[-1][:, 0].mean()) if losses else float("nan")
     loss_first = float(first_timed[0]) if first_timed else float("nan")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step holds after its last step: the logits and per-row {loss, top1, top5} of
+        # the last batch, its gradient, and the parameters and momentum after the update (before --full's extra
+        # steps touch them)
+        dump_outputs(args.dump_outputs, {"logits": eng.acts(b).logits, "row_stats": losses[-1], "grad": eng.grad,
+                                         "params": eng.flat, "momentum": mom_buf})
+    # --full: the roofline entries, from two more (eager) probe steps after the timed region
+    roof = roofline_entries(args, eng, ops, cfg, b, step_body, barrier, hyper, hyper_all[total_steps - 1]) \
+        if args.full else {}
+    dist_check = None
+    if world > 1:
+        dist_check = replica_check(eng.flat, dt, args.steps, world, backend, dev)
+        dt = dist_check.pop("_dt_max")
+        if args.full:
+            ops.copy2d(hyper, 12, hyper_all[total_steps - 1], 12, 12, 1)
+            dist_check["exchange"] = exchange_check(step_body, reducer, dt, args.steps, world, dev, barrier)
+    imgs = args.steps * b * world
+    value = imgs / dt
+    fpi = train_flops_per_image(arch, args.image_size, args.num_classes)
+    # executed work: with the last layer pruned to its cls rows (engine.prune_last, only they reach
+    # the classifier) its out-proj / fc1 / fc2 skip N-1 tokens per image in forward, dgrad and wgrad
+    D_, M_, N_ = cfg.emb_dim, cfg.mlp_dim, cfg.tokens
+    # (and its attention computes only the first 32-query pair: (N - 32) / N of QK^T / PV forward and
+    # backward is skipped as well)
+    q_kept = min(N_, 32)
+    fpe = fpi - ((3 * 2 * (N_ - 1) * (D_ * D_ + 2 * D_ * M_) + 3 * 4 * (N_ - q_kept) * N_ * D_)
+                 if eng.prune_last else 0)
+    step_tflops_per_gpu = value / world * fpi / 1e12
+    out = {
+        "metric": "images/sec training step, ViT-B/16 224px bf16, 1/2/4/8 MI355X" if args.arch == "b16" and
+        args.image_size == 224 else f"images/sec training step, ViT-{args.arch} {args.image_size}px bf16",
+        "value": round(value, 2),
+        "unit": "images/sec",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": ("synthetic (N(0,1) images, uniform labels, seed-42 reference-order random init" +
+                 (", attention projections at N(0,1/D) and pos-emb / classifier at N(0,0.02^2): bench.condition_init)"
+                  if init_kind != "reference" else ")")),
+        "loss_first_timed_step": round(loss_first, 5), "loss_last_timed_step": round(loss_last, 5),
+        "config": {"workload": f"ViT-{args.arch.upper()} @{args.image_size} train step (fwd+CE+bwd+"
+                               f"{comm + ' all-reduce+' if world > 1 else ''}SGD-momentum/OneCycleLR)",
+                   "model": f"ViT-{args.arch.upper()}", "image_size": args.image_size, "per_gpu_batch": b,
+                   "global_batch": b * world, "seq_len": cfg.tokens, "num_classes": args.num_classes,
+                   "parallelism": f"dp{world}", "dist_backend": backend,
+                   "step_launch": "one HIP graph per step" if use_graph else "eager",
+                   **({"grad_allreduce_dtype": "bf16"} if compress and world > 1 else {})},
+        **roof,
+        "step_mfma_frac": round(value / world * fpe / 1e12 / PEAK_BF16_TFLOPS, 4),
+        "step_mfma_frac_algorithmic": round(step_tflops_per_gpu / PEAK_BF16_TFLOPS, 4),
+        "train_gflop_per_image": round(fpi / 1e9, 3),
+        "executed_gflop_per_image": round(fpe / 1e9, 3),
+    }
+    if dist_check is not None:
+        out["dist_check"] = dist_check
+    if args.full and world == 1 and os.environ.get("VITMI_BENCH_TRAIN_EPOCH", "1") != "0":
+        # the drop-in path (train_epoch + vitmi.optim.SGD + OneCycleLR + metrics) at the same shape, after the engine
+        # loop: how much of `value` a user of the reference's entry point sees
+        te, te_res = time_train_epoch(model, b, args.image_size, args.num_classes, args.steps, args.warmup, dev)
+        out["train_epoch_img_s"] = round(te, 2)
+        out["train_epoch_vs_value"] = round(te / value, 4)
+        out["train_epoch_note"] = ("vitmi.train.train_epoch (src/train.py:12-37) + vitmi.optim.SGD + torch OneCycleLR + "
+                                   f"loss/acc1/acc5 metrics, {args.steps} synthetic HBM-resident batches of {b} after a "
+                                   f"{args.warmup}-batch epoch; last epoch loss {te_res['loss']:.4f}")
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(arch, args.image_size, args.num_classes, args.cpu_seconds)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+        if not dist_check["replicas_identical"]:
+            print("error: the data-parallel replicas' parameters differ after the run", file=sys.stderr)
+            sys.exit(3)
+
+
+def roofline_entries(args, eng, ops, cfg, b, step_body, barrier, hyper, hyper_last):
+    """--full: the "roofline*" entries of the result line. Two more eager steps after the timed region (each with
+    the last timed step's OneCycleLR scalars, hyper_last) with HIP events around the roofline kernels' launches,
+    and the HBM traffic of those kernels from the committed PMC passes."""
     # HIP events around the roofline kernels' launches of one more (eager) step after the timed region,
     # on the stream the kernels run on (each event record costs the stream ~10 us of idle)
     probes = ([], [])
     eng.probe, eng.probe_wgrad = probes
-    ops.copy2d(hyper, 12, hyper_all[total_steps - 1], 12, 12, 1)
+    ops.copy2d(hyper, 12, hyper_last, 12, 12, 1)
     step_body()
     barrier()
     probe, probe_w = probes
@@ -345,16 +463,10 @@ def main():
     # events would otherwise land inside these)
     T = b * cfg.tokens
     ops.GEMM_PROBE, ops.GEMM_PROBE_MIN_M = [], T
-    ops.copy2d(hyper, 12, hyper_all[total_steps - 1], 12, 12, 1)
+    ops.copy2d(hyper, 12, hyper_last, 12, 12, 1)
     step_body()
     barrier()
     probe_fd, ops.GEMM_PROBE = ops.GEMM_PROBE, None
-    dist_check = None
-    if world > 1:
-        dist_check = replica_check(eng.flat, dt, args.steps, world, backend, dev)
-        dt = dist_check.pop("_dt_max")
-        ops.copy2d(hyper, 12, hyper_all[total_steps - 1], 12, 12, 1)
-        dist_check["exchange"] = exchange_check(step_body, reducer, dt, args.steps, world, dev, barrier)
     fc1_ms = sum(s.elapsed_time(e) for s, e in probe) / max(1, len(probe))
     fd_ms = [s_.elapsed_time(e_) for s_, e_, _, _ in probe_fd]
     fd_flop = sum(p_[2] for p_ in probe_fd)
@@ -386,17 +498,6 @@ def main():
     wg_tflops = wg_flop / (sum(wg_ms) * 1e-3) / 1e12 if wg_ms else 0.0
     wg_avg_ms = sum(wg_ms) / max(1, len(wg_ms))
     pr_ms = sum(p_[0].elapsed_time(p_[1]) for p_ in pr_w)
-    imgs = args.steps * b * world
-    value = imgs / dt
-    fpi = train_flops_per_image(arch, args.image_size, args.num_classes)
-    # executed work: with the last layer pruned to its cls rows (engine.prune_last, only they reach
-    # the classifier) its out-proj / fc1 / fc2 skip N-1 tokens per image in forward, dgrad and wgrad
-    D_, M_, N_ = cfg.emb_dim, cfg.mlp_dim, cfg.tokens
-    # (and its attention computes only the first 32-query pair: (N - 32) / N of QK^T / PV forward and
-    # backward is skipped as well)
-    q_kept = min(N_, 32)
-    fpe = fpi - ((3 * 2 * (N_ - 1) * (D_ * D_ + 2 * D_ * M_) + 3 * 4 * (N_ - q_kept) * N_ * D_)
-                 if eng.prune_last else 0)
     traffic = pmc_traffic() if args.arch == "b16" and b == 256 else None
     traffic_w = None
     if args.arch == "b16" and b == 256:
@@ -410,31 +511,7 @@ def main():
                                                             "gemm_pp2_group_kernel": t_grp},
                          "launches": {"gemm_pp2_kernel<false, false, 7>": n_all - n_group,
                                       "gemm_pp2_group_kernel": n_group}}
-    step_tflops_per_gpu = value / world * fpi / 1e12
-    out = {
-        "metric": "images/sec training step, ViT-B/16 224px bf16, 1/2/4/8 MI355X" if args.arch == "b16" and
-        args.image_size == 224 else f"images/sec training step, ViT-{args.arch} {args.image_size}px bf16",
-        "value": round(value, 2),
-        "unit": "images/sec",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": ("synthetic (N(0,1) images, uniform labels, seed-42 reference-order random init" +
-                 (", attention projections at N(0,1/D) and pos-emb / classifier at N(0,0.02^2): bench.condition_init)"
-                  if init_kind != "reference" else ")")),
-        "loss_first_timed_step": round(loss_first, 5), "loss_last_timed_step": round(loss_last, 5),
-        "config": {"workload": f"ViT-{args.arch.upper()} @{args.image_size} train step (fwd+CE+bwd+"
-                               f"{comm + ' all-reduce+' if world > 1 else ''}SGD-momentum/OneCycleLR)",
-                   "model": f"ViT-{args.arch.upper()}", "image_size": args.image_size, "per_gpu_batch": b,
-                   "global_batch": b * world, "seq_len": cfg.tokens, "num_classes": args.num_classes,
-                   "parallelism": f"dp{world}", "dist_backend": backend,
-                   "step_launch": "one HIP graph per step" if use_graph else "eager",
-                   **({"grad_allreduce_dtype": "bf16"} if compress and world > 1 else {})},
+    return {
         "roofline": {"bound": "mfma", "kernel": "split-K weight-gradient GEMMs (the step's dominant kernel family): "
                                                 f"the {len(wg_ms)} launches over all tokens of one step (HIP events, an "
                                                 f"eager step after the timed region), K = {T} tokens padded to 64; fc1 "
@@ -463,32 +540,7 @@ def main():
                                "frac": round(fd_tflops / PEAK_BF16_TFLOPS, 4), "traffic": None,
                                "calls": len(fd_ms), "total_ms": round(sum(fd_ms), 4),
                                "gflop_per_step": round(fd_flop / 1e9, 2), "by_epilogue": fd_by_epi},
-        "step_mfma_frac": round(value / world * fpe / 1e12 / PEAK_BF16_TFLOPS, 4),
-        "step_mfma_frac_algorithmic": round(step_tflops_per_gpu / PEAK_BF16_TFLOPS, 4),
-        "train_gflop_per_image": round(fpi / 1e9, 3),
-        "executed_gflop_per_image": round(fpe / 1e9, 3),
     }
-    if dist_check is not None:
-        out["dist_check"] = dist_check
-    if world == 1 and os.environ.get("VITMI_BENCH_TRAIN_EPOCH", "1") != "0":
-        # the drop-in path (train_epoch + vitmi.optim.SGD + OneCycleLR + metrics) at the same shape, after the engine
-        # loop: how much of `value` a user of the reference's entry point sees
-        te, te_res = time_train_epoch(model, b, args.image_size, args.num_classes, args.steps, args.warmup, dev)
-        out["train_epoch_img_s"] = round(te, 2)
-        out["train_epoch_vs_value"] = round(te / value, 4)
-        out["train_epoch_note"] = ("vitmi.train.train_epoch (src/train.py:12-37) + vitmi.optim.SGD + torch OneCycleLR + "
-                                   f"loss/acc1/acc5 metrics, {args.steps} synthetic HBM-resident batches of {b} after a "
-                                   f"{args.warmup}-batch epoch; last epoch loss {te_res['loss']:.4f}")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(arch, args.image_size, args.num_classes, args.cpu_seconds)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
-        if not dist_check["replicas_identical"]:
-            print("error: the data-parallel replicas' parameters differ after the run", file=sys.stderr)
-            sys.exit(3)
 
 
 def replica_hash(flat):
@@ -673,12 +725,14 @@ def bench_resvit(args, world, rank, dev, backend, comm):
     graphed = None if eager else GraphedTrainStep(model, x, y, opt, sched, 1e-4, 1e-2, 1.0, True, reducer=reducer)
 
     totals = []
+    last = []  # the last step's returned tuple
 
     def step():
         out = graphed.step() if graphed is not None else train_step(model, x, y, opt, sched, 1e-4, 1e-2, 1.0, True,
                                                                     reducer)
         ratios.append(out[5]["non_low_rank_ratio"].clone())
         totals.append(out[0].detach().clone())
+        last[:] = out
 
     def barrier():
         if world > 1:
@@ -694,6 +748,11 @@ def bench_resvit(args, world, rank, dev, backend, comm):
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step's returned losses and router entropy, and the trainable parameters after its update
+        dump_outputs(args.dump_outputs, {"total_loss": totals[-1], "class_loss": last[1], "active_loss": last[2],
+                                         "distill_loss": last[3], "router_entropy": last[4],
+                                         "active_ratio": ratios[-1], "params": opt.flat.data})
     dist_check = None
     if world > 1:  # the trainable flat buffer (LoRA, routers, approximators, head): the frozen bases never change
         dist_check = replica_check(opt.flat.data, dt, args.steps, world, backend, dev)

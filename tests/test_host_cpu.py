@@ -163,3 +163,24 @@ def test_bench_condition_init_is_the_parity_rescale():
     sd = m.state_dict()
     assert sd.keys() == ref.keys()
     assert all(torch.equal(sd[k], ref[k]) for k in ref)
+
+
+def test_bench_dump_outputs_is_float32_and_samples_large_arrays_reproducibly(tmp_path):
+    """bench.dump_outputs (--dump-outputs): small arrays whole, an array over DUMP_SAMPLE elements as the same
+    seeded sample of its elements on every call, everything float32 on disk (float64 kept)"""
+    import sys
+    sys.path.insert(0, REPO)
+    import bench
+    import numpy as np
+    big = torch.arange(bench.DUMP_SAMPLE * 3 + 5, dtype=torch.float32)
+    small = torch.arange(12, dtype=torch.bfloat16).reshape(3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small, "f64": small.double(), "scalar": 1.5})
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("big", "small", "f64", "scalar")}
+    assert a["small"].dtype == np.float32 and a["small"].shape == (3, 4)
+    assert np.array_equal(a["small"], small.float().numpy())
+    assert a["f64"].dtype == np.float64 and a["scalar"].dtype == np.float32 and float(a["scalar"]) == 1.5
+    assert a["big"].dtype == np.float32 and a["big"].shape == (bench.DUMP_SAMPLE,)
+    assert np.all(np.diff(a["big"]) >= 0) and a["big"].max() > 2.5 * bench.DUMP_SAMPLE  # sorted, over the whole range
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20

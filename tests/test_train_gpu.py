@@ -283,3 +283,37 @@ def test_eval_accuracy_matches_oracle_at_577_tokens():
         r5.append(float(a5))
     ref1, ref5 = sum(r1) / 3, sum(r5) / 3
     assert abs(acc1 - ref1) < 1e-4 and abs(acc5 - ref5) < 1e-4, (acc1, acc5, ref1, ref5)
+
+
+@pytest.mark.parametrize("full", [False, True], ids=["plain", "full"])
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, full):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (config C1's small shape): the result line holds the
+    headline fields and ms_per_step = 1000 * batch / value, DIR holds the last timed step's arrays in float32,
+    and the roofline / train_epoch / CPU-baseline entries appear with --full only."""
+    import json
+
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--arch", "b32",
+           "--image-size", "32", "--batch", "32", "--num-classes", "100", "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd + (["--full", "--cpu-seconds", "1"] if full else []), env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    out = json.loads(lines[0])
+    assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0
+    assert out["ms_per_step"] == pytest.approx(1e3 * 32 / out["value"], rel=1e-3)
+    extra = {"roofline", "roofline_fc1_fwd", "roofline_fwd_dgrad", "train_epoch_img_s", "cpu_baseline"}
+    assert extra <= out.keys() if full else not (extra & out.keys())
+    dump = {f[:-4]: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert sorted(dump) == ["grad", "logits", "momentum", "params", "row_stats"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in dump.values())
+    assert dump["logits"].shape == (32, 100) and dump["row_stats"].shape[0] == 32
+    assert dump["grad"].shape == dump["params"].shape == dump["momentum"].shape
+    assert np.abs(dump["grad"]).max() > 0 and np.abs(dump["momentum"]).max() > 0
+    # the dumped per-row losses are the last timed step's: their mean is the line's loss_last_timed_step
+    assert float(dump["row_stats"][:, 0].mean()) == pytest.approx(out["loss_last_timed_step"], abs=2e-5)
+    assert sum(v.nbytes for v in dump.values()) <= 64 << 20

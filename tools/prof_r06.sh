@@ -17,9 +17,9 @@ if [ "$2" != "skip-tests" ]; then
   step "smoke" timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
   tail -1 $O/smoke.log
 fi
-step "bench" env VITMI_BENCH_TRAIN_EPOCH=1 timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 > $O/bench_b16.json 2> $O/bench_b16.err
+step "bench" env VITMI_BENCH_TRAIN_EPOCH=1 timeout -k 10 300 python3 -u bench.py --full --steps 20 --warmup 5 > $O/bench_b16.json 2> $O/bench_b16.err
 tail -c 400 $O/bench_b16.json; echo
-step "ktrace" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace -o run -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/ktrace.log 2>&1
+step "ktrace" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace -o run -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/ktrace.log 2>&1
 S=$(find $O/ktrace -name "*kernel_stats.csv" | head -1)
 T=$(find $O/ktrace -name "*kernel_trace.csv" | head -1)
 python3 tools/prof_summary.py $S 13 > $O/kernel_summary.txt
@@ -27,9 +27,9 @@ python3 tools/trace_step.py $T 3 $O/step_launches.txt > $O/step_timeline.txt
 cp $S $O/kernel_stats.csv
 rm -rf $O/ktrace
 RX='gemm_pp2_kernel<false, false, 7|gemm_pp2_group_kernel|gemm_\w+_kernel<.*true, true, 8|attn_bwd_pers_kernel'
-step "pmc fetch" timeout -k 10 -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$RX" --output-format csv -d $O/fetch -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch.log 2>&1
-step "pmc write" timeout -k 10 -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$RX" --output-format csv -d $O/write -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/write.log 2>&1
-step "pmc mfma" timeout -k 10 -s KILL 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --kernel-include-regex "$RX" --output-format csv -d $O/mfma -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/mfma.log 2>&1
+step "pmc fetch" timeout -k 10 -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$RX" --output-format csv -d $O/fetch -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch.log 2>&1
+step "pmc write" timeout -k 10 -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$RX" --output-format csv -d $O/write -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/write.log 2>&1
+step "pmc mfma" timeout -k 10 -s KILL 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --kernel-include-regex "$RX" --output-format csv -d $O/mfma -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/mfma.log 2>&1
 F=$(find $O/fetch -name "*counter_collection.csv" | head -1)
 W=$(find $O/write -name "*counter_collection.csv" | head -1)
 M=$(find $O/mfma -name "*counter_collection.csv" | head -1)
