@@ -249,6 +249,15 @@ int vit_attention_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t 
  * ---------------------------------------------------------------------------------------- */
 int vit_im2col(const float* x, void* out, int64_t B, int64_t img, int64_t P, int64_t Kpad,
                vit_stream_t stream);
+/* The same for any image and patch rectangle (src/model.py:173-179: image_size=(h, w), patch_size=(fh, fw)):
+ * x f32 NCHW [B,3,H,W] -> out bf16 [B*N, Kpad], gh = H/Ph, gw = W/Pw (floor, as Conv2d does),
+ * N = gh*gw + 1. Row b*N + 1 + py*gw + px, col c*Ph*Pw + ky*Pw + kx holds x[b][c][py*Ph+ky][px*Pw+kx];
+ * the cls row b*N and the cols >= 3*Ph*Pw are written as 0; pixels past gh*Ph / gw*Pw are never read.
+ * H < Ph, W < Pw, Kpad < 3*Ph*Pw or a null pointer: VIT_ERR_INVALID_ARG, nothing launched.
+ * Pw % 8 == 0, W % 4 == 0, Kpad == 3*Ph*Pw and 16-B aligned x / out take the 8-wide vector kernel, everything
+ * else the scalar one; vit_im2col(img, P) is vit_im2col_hw(img, img, P, P). */
+int vit_im2col_hw(const float* x, void* out, int64_t B, int64_t H, int64_t W, int64_t Ph, int64_t Pw, int64_t Kpad,
+                  vit_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------
  * Training-input transform (src/data_loaders.py:66-80 CIFAR train, :100-112 ImageNet):
@@ -364,6 +373,9 @@ int vit_axpby(const float* x, float* y, int64_t n, float a, float b, vit_stream_
 /* out f32 [B*N, Kpad]: as vit_im2col (src/model.py:179,197-200) without the bf16 rounding */
 int vit_im2col_f32(const float* x, float* out, int64_t B, int64_t img, int64_t P, int64_t Kpad,
                    vit_stream_t stream);
+/* out f32 [B*N, Kpad]: as vit_im2col_hw without the bf16 rounding */
+int vit_im2col_hw_f32(const float* x, float* out, int64_t B, int64_t H, int64_t W, int64_t Ph, int64_t Pw,
+                      int64_t Kpad, vit_stream_t stream);
 /* h[b*N+t] = (t == 0 ? cls : h[b*N+t]) + pos[t]   (src/model.py:203-204, :16-17) */
 int vit_embed_fwd_f32(float* h, int64_t B, int64_t N, int64_t D, const float* pos, const float* cls,
                       vit_stream_t stream);

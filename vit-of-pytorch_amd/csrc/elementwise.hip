@@ -5,14 +5,16 @@
 
 namespace {
 
-// ---- im2col for Conv2d(3, D, k=P, s=P) (reference src/model.py:179,197-200) ----------------------
-// out[b*N + 1 + py*g + px][c*P*P + ky*P + kx] = x[b][c][py*P+ky][px*P+kx]; cls rows and pad cols = 0.
+// ---- im2col for Conv2d(3, D, k=s=(Ph,Pw)) (reference src/model.py:173-179,197-200) --------------
+// gh = H/Ph, gw = W/Pw (floor), N = gh*gw + 1.
+// out[b*N + 1 + py*gw + px][c*Ph*Pw + ky*Pw + kx] = x[b][c][py*Ph+ky][px*Pw+kx]; cls rows and pad cols = 0.
 template <typename OUT>
-__global__ void im2col_kernel(const float* __restrict__ x, OUT* __restrict__ out, int B, int img, int P, int Kpad) {
-  const int g = img / P;
-  const int N = g * g + 1;
+__global__ void im2col_kernel(const float* __restrict__ x, OUT* __restrict__ out, int B, int H, int W, int Ph, int Pw,
+                              int Kpad) {
+  const int gw = W / Pw;
+  const int N = (H / Ph) * gw + 1;
   const long total = (long)B * N * Kpad;
-  const int K = 3 * P * P;
+  const int PP = Ph * Pw, K = 3 * PP;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int col = (int)(i % Kpad);
     const long row = i / Kpad;
@@ -20,9 +22,9 @@ __global__ void im2col_kernel(const float* __restrict__ x, OUT* __restrict__ out
     const int b = (int)(row / N);
     float v = 0.f;
     if (t > 0 && col < K) {
-      const int patch = t - 1, py = patch / g, px = patch % g;
-      const int c = col / (P * P), rem = col % (P * P), ky = rem / P, kx = rem % P;
-      v = x[(((long)b * 3 + c) * img + (py * P + ky)) * img + (px * P + kx)];
+      const int patch = t - 1, py = patch / gw, px = patch % gw;
+      const int c = col / PP, rem = col % PP, ky = rem / Pw, kx = rem % Pw;
+      v = x[(((long)b * 3 + c) * H + (py * Ph + ky)) * W + (px * Pw + kx)];
     }
     if constexpr (sizeof(OUT) == 2)
       out[i] = f2bf(v);
@@ -53,12 +55,15 @@ __global__ void dropout_mask_kernel(DropDev drop, long row0, long rows, int cols
   out[r * ld + c] = drop.thr ? drop_mult1(drop, row0 + r, c) : 1.0f;
 }
 
-// Vector forms of the two embedding kernels above (the common shapes: P % 8 == 0, D % 4 == 0).
+// Vector forms of the two embedding kernels above (the common shapes: Pw % 8 == 0, D % 4 == 0).
 // im2col: one thread per 8 consecutive patch columns (8 adjacent pixels of one image row: two
 // 16-B loads, one 16-B bf16 store); the division chain runs once per 8 outputs instead of per output.
+// A source run starts at float (py*Ph+ky)*W + px*Pw + kx past a 16-B aligned plane: Pw % 8 == 0 keeps
+// kx and px*Pw multiples of 8, W % 4 == 0 keeps every image row 16-B aligned; H and Ph do not enter.
 template <typename OUT>
-__global__ void im2col8_kernel(const float* __restrict__ x, OUT* __restrict__ out, int B, int img, int P) {
-  const int g = img / P, N = g * g + 1, K8 = 3 * P * P / 8;
+__global__ void im2col8_kernel(const float* __restrict__ x, OUT* __restrict__ out, int B, int H, int W, int Ph,
+                               int Pw) {
+  const int gw = W / Pw, N = (H / Ph) * gw + 1, PP = Ph * Pw, K8 = 3 * PP / 8;
   const long total = (long)B * N * K8;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int c8 = (int)(i % K8);
@@ -66,10 +71,10 @@ __global__ void im2col8_kernel(const float* __restrict__ x, OUT* __restrict__ ou
     const int t = (int)(row % N), b = (int)(row / N);
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
     if (t > 0) {
-      const int patch = t - 1, py = patch / g, px = patch % g;
-      const int col = c8 * 8, c = col / (P * P), rem = col % (P * P), ky = rem / P, kx = rem % P;
+      const int patch = t - 1, py = patch / gw, px = patch % gw;
+      const int col = c8 * 8, c = col / PP, rem = col % PP, ky = rem / Pw, kx = rem % Pw;
       const float4* src =
-          reinterpret_cast<const float4*>(x + (((long)b * 3 + c) * img + (py * P + ky)) * img + (px * P + kx));
+          reinterpret_cast<const float4*>(x + (((long)b * 3 + c) * H + (py * Ph + ky)) * W + (px * Pw + kx));
       lo = src[0];
       hi = src[1];
     }
@@ -453,18 +458,43 @@ unsigned grid_for(long n, int per_thread = 1) {
   return (unsigned)b;
 }
 
+// 8-wide vector form (im2col8_kernel) or the scalar one; OUT = bf16_t / float
+template <typename OUT>
+void im2col_launch(const float* x, OUT* out, int64_t B, int64_t H, int64_t W, int64_t Ph, int64_t Pw, int64_t Kpad,
+                   hipStream_t s) {
+  const int64_t N = (H / Ph) * (W / Pw) + 1;
+  if (Pw % 8 == 0 && W % 4 == 0 && Kpad == 3 * Ph * Pw && (uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0)
+    hipLaunchKernelGGL(im2col8_kernel<OUT>, dim3(grid_for(B * N * Kpad / 8)), dim3(256), 0, s, x, out, (int)B, (int)H,
+                       (int)W, (int)Ph, (int)Pw);
+  else
+    hipLaunchKernelGGL(im2col_kernel<OUT>, dim3(grid_for(B * N * Kpad)), dim3(256), 0, s, x, out, (int)B, (int)H,
+                       (int)W, (int)Ph, (int)Pw, (int)Kpad);
+}
+
 }  // namespace
+
+extern "C" int vit_im2col_hw(const float* x, void* out, int64_t B, int64_t H, int64_t W, int64_t Ph, int64_t Pw,
+                             int64_t Kpad, vit_stream_t stream) {
+  VIT_CHECK_ARG(x && out && B > 0 && Ph > 0 && Pw > 0 && H >= Ph && W >= Pw && Kpad >= 3 * Ph * Pw &&
+                    3 * H * W < (1L << 31) && Kpad < (1L << 31),
+                "vit_im2col_hw: bad args");
+  im2col_launch(x, (bf16_t*)out, B, H, W, Ph, Pw, Kpad, (hipStream_t)stream);
+  VIT_LAUNCH_CHECK("vit_im2col_hw");
+}
+
+extern "C" int vit_im2col_hw_f32(const float* x, float* out, int64_t B, int64_t H, int64_t W, int64_t Ph, int64_t Pw,
+                                 int64_t Kpad, vit_stream_t stream) {
+  VIT_CHECK_ARG(x && out && B > 0 && Ph > 0 && Pw > 0 && H >= Ph && W >= Pw && Kpad >= 3 * Ph * Pw &&
+                    3 * H * W < (1L << 31) && Kpad < (1L << 31),
+                "vit_im2col_hw_f32: bad args");
+  im2col_launch(x, out, B, H, W, Ph, Pw, Kpad, (hipStream_t)stream);
+  VIT_LAUNCH_CHECK("vit_im2col_hw_f32");
+}
 
 extern "C" int vit_im2col(const float* x, void* out, int64_t B, int64_t img, int64_t P, int64_t Kpad,
                           vit_stream_t stream) {
   VIT_CHECK_ARG(x && out && B > 0 && P > 0 && img >= P && Kpad >= 3 * P * P, "vit_im2col: bad args");
-  const int64_t g = img / P, N = g * g + 1;
-  if (P % 8 == 0 && img % 4 == 0 && Kpad == 3 * P * P && (uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0)
-    hipLaunchKernelGGL(im2col8_kernel<bf16_t>, dim3(grid_for(B * N * Kpad / 8)), dim3(256), 0, (hipStream_t)stream, x,
-                       (bf16_t*)out, (int)B, (int)img, (int)P);
-  else
-    hipLaunchKernelGGL(im2col_kernel<bf16_t>, dim3(grid_for(B * N * Kpad)), dim3(256), 0, (hipStream_t)stream, x,
-                       (bf16_t*)out, (int)B, (int)img, (int)P, (int)Kpad);
+  im2col_launch(x, (bf16_t*)out, B, img, img, P, P, Kpad, (hipStream_t)stream);
   VIT_LAUNCH_CHECK("vit_im2col");
 }
 
@@ -926,13 +956,7 @@ __global__ void gelu_f32_kernel(const float* __restrict__ in, float* __restrict_
 extern "C" int vit_im2col_f32(const float* x, float* out, int64_t B, int64_t img, int64_t P, int64_t Kpad,
                               vit_stream_t stream) {
   VIT_CHECK_ARG(x && out && B > 0 && P > 0 && img >= P && Kpad >= 3 * P * P, "vit_im2col_f32: bad args");
-  const int64_t g = img / P, N = g * g + 1;
-  if (P % 8 == 0 && img % 4 == 0 && Kpad == 3 * P * P && (uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0)
-    hipLaunchKernelGGL(im2col8_kernel<float>, dim3(grid_for(B * N * Kpad / 8)), dim3(256), 0, (hipStream_t)stream, x,
-                       out, (int)B, (int)img, (int)P);
-  else
-    hipLaunchKernelGGL(im2col_kernel<float>, dim3(grid_for(B * N * Kpad)), dim3(256), 0, (hipStream_t)stream, x, out,
-                       (int)B, (int)img, (int)P, (int)Kpad);
+  im2col_launch(x, out, B, img, img, P, P, Kpad, (hipStream_t)stream);
   VIT_LAUNCH_CHECK("vit_im2col_f32");
 }
 

@@ -18,6 +18,7 @@ Only safe loaders are used: numpy with allow_pickle=False, torch.load with weigh
 The result feeds `VisionTransformer.load_state_dict`, whose parameters are views of the engine's
 flat buffer; the bf16 GEMM mirror is rebuilt on the next forward (parameter versions change).
 """
+import math
 import os
 
 import numpy as np
@@ -105,4 +106,48 @@ def save_jax_to_pytorch(jax_path, save_path):
     state_dict = convert_jax_pytorch(*load_jax(jax_path))
     out = os.path.join(save_path, model_name + ".pth")
     torch.save({"state_dict": state_dict}, out)
+    return out
+
+
+POS_EMBEDDING_KEY = "transformer.pos_embedding.pos_embedding"
+
+
+def _lerp_axis(t, g_new, dim):
+    """bilinear resample of t along dim to g_new samples, half-pixel centres, edges clamped"""
+    g = t.shape[dim]
+    s = ((torch.arange(g_new, dtype=torch.float32) + 0.5) * (g / g_new) - 0.5).clamp_(0, g - 1)
+    i0 = s.floor().long()
+    i1 = (i0 + 1).clamp_(max=g - 1)
+    shape = [1] * t.dim()
+    shape[dim] = g_new
+    w = (s - i0.float()).view(shape)
+    return t.index_select(dim, i0) * (1 - w) + t.index_select(dim, i1) * w
+
+
+def resize_pos_embedding(state_dict, new_grid, old_grid=None, key=POS_EMBEDDING_KEY):
+    """A copy of state_dict whose position table [1, 1 + gh*gw, D] is resampled to new_grid = (gh', gw'): the way
+    to load a checkpoint into a model of another patch grid (224 -> 384, square -> rectangular), where
+    load_state_dict alone refuses the table's shape. The cls row is copied; the gh x gw patch rows are
+    resampled separably and bilinearly in f32 with half-pixel centres (output index i samples
+    s = (i + 0.5) g / g' - 0.5 clamped to [0, g - 1]: rows i0 = floor(s) and min(i0 + 1, g - 1), weight s - i0),
+    rows first, then columns. old_grid None: the square grid sqrt(rows - 1). The same grid returns the table
+    unchanged. Host arithmetic at load time; nothing calls it unless asked to."""
+    pos = state_dict[key]
+    if pos.dim() != 3 or pos.shape[0] != 1:
+        raise ValueError(f"{key}: expected [1, tokens, D], got {tuple(pos.shape)}")
+    rows, d = pos.shape[1] - 1, pos.shape[2]
+    if old_grid is None:
+        g = math.isqrt(max(rows, 0))
+        if g * g != rows:
+            raise ValueError(f"{key}: {rows} patch rows are no square grid; pass old_grid=(gh, gw)")
+        old_grid = (g, g)
+    (gh, gw), (nh, nw) = (int(v) for v in old_grid), (int(v) for v in new_grid)
+    if gh * gw != rows or min(gh, gw, nh, nw) < 1:
+        raise ValueError(f"{key}: {rows} patch rows are not a {gh}x{gw} grid, or an empty grid was asked for")
+    out = type(state_dict)(state_dict)
+    if (gh, gw) == (nh, nw):
+        return out
+    p = pos.detach().to("cpu", torch.float32)
+    grid = _lerp_axis(_lerp_axis(p[0, 1:].view(gh, gw, d), nh, 0), nw, 1)
+    out[key] = torch.cat([p[:, :1], grid.reshape(1, nh * nw, d)], dim=1).to(pos.dtype)
     return out

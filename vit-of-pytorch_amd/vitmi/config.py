@@ -7,6 +7,10 @@ src/config.py:57-104). Additions for the MI355X path, all optional:
   --synthetic-source-size  >0: synthetic uint8 HWC images of this size, resized / flipped /
                          normalised on the device like the reference's CIFAR transform (vitmi.data)
   --any-image-size       lift the reference's choices=[224, 384] on --image-size (src/config.py:37)
+  --image-size HxW       a rectangular input such as 224x384 (needs --any-image-size); config.image_size is then the
+                         pair (224, 384); a plain int stays an int
+  --resize-pos-embedding resample a checkpoint's position table to the model's patch grid when they differ
+                         (vitmi.checkpoint.resize_pos_embedding)
   --no-save              do not create experiments/ directories or checkpoints
   --precision            (eval) bf16 MFMA forward (default) or the reference's f32 arithmetic
 """
@@ -34,8 +38,27 @@ def _add_common(parser, train: bool):
     parser.add_argument("--any-image-size", default=False, action="store_true", help="allow any --image-size")
 
 
+def _image_size(text):
+    """'224' -> 224, '224x384' -> (224, 384)"""
+    try:
+        if "x" in text.lower():
+            h, w = text.lower().split("x")
+            return int(h), int(w)
+        return int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: expected an int or HxW, such as 224 or 224x384") from None
+
+
+def image_hw(image_size):
+    """(h, w) of config.image_size: an int (square) or an (h, w) pair"""
+    return (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
+
+
 def _image_size_arg(parser, default):
-    parser.add_argument("--image-size", type=int, default=default, help="input image size")
+    parser.add_argument("--image-size", type=_image_size, default=default,
+                        help="input image size: an int, or HxW with --any-image-size")
+    parser.add_argument("--resize-pos-embedding", default=False, action="store_true",
+                        help="resample the checkpoint's position embeddings to this model's patch grid")
 
 
 def get_eval_config(argv=None):

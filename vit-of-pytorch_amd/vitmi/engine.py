@@ -41,23 +41,57 @@ _NBUF = 2
 _WGRAD_TARGET = int(os.environ.get("VIT_WGRAD_TARGET", "256"))
 
 
+def _hw(v):
+    """(h, w) of an int (square) or an (h, w) pair"""
+    if isinstance(v, int):
+        return v, v
+    h, w = v
+    return int(h), int(w)
+
+
 @dataclass(frozen=True)
 class ArchConfig:
-    image_size: int = 224
-    patch_size: int = 16
+    """image_size / patch_size: an int (square) or an (h, w) / (fh, fw) pair (reference src/model.py:173-179).
+    Height and width stop at the patch embedding; everything after it sees `tokens`."""
+    image_size: int | tuple = 224
+    patch_size: int | tuple = 16
     emb_dim: int = 768
     mlp_dim: int = 3072
     num_heads: int = 12
     num_layers: int = 12
     num_classes: int = 1000
 
+    def __post_init__(self):
+        for f in ("image_size", "patch_size"):
+            v = getattr(self, f)
+            if not isinstance(v, int):  # lists hash badly: keep pairs as tuples of ints
+                object.__setattr__(self, f, _hw(v))
+
+    @property
+    def image_hw(self):
+        return _hw(self.image_size)
+
+    @property
+    def patch_hw(self):
+        return _hw(self.patch_size)
+
+    @property
+    def grid_hw(self):
+        # Conv2d(k=s=(fh, fw)) floors non-divisible sizes (reference src/model.py:174-178)
+        (h, w), (fh, fw) = self.image_hw, self.patch_hw
+        return h // fh, w // fw
+
     @property
     def grid(self):
-        return self.image_size // self.patch_size
+        gh, gw = self.grid_hw
+        if gh != gw:
+            raise ValueError(f"ArchConfig.grid is the side of a square patch grid; this one is {gh}x{gw} (use grid_hw)")
+        return gh
 
     @property
     def tokens(self):
-        return self.grid * self.grid + 1
+        gh, gw = self.grid_hw
+        return gh * gw + 1
 
     @property
     def head_dim(self):
@@ -65,7 +99,8 @@ class ArchConfig:
 
     @property
     def patch_k(self):
-        return 3 * self.patch_size * self.patch_size
+        fh, fw = self.patch_hw
+        return 3 * fh * fw
 
 
 def layer_param_specs(cfg: ArchConfig, i: int):
@@ -85,12 +120,12 @@ def layer_param_specs(cfg: ArchConfig, i: int):
 
 def flat_param_specs(cfg: ArchConfig):
     """All parameters in flat-buffer order (reverse of backward completion)."""
-    D, P, C = cfg.emb_dim, cfg.patch_size, cfg.num_classes
+    D, C = cfg.emb_dim, cfg.num_classes
     specs = [("classifier.weight", (C, D)), ("classifier.bias", (C,)),
              ("transformer.norm.weight", (D,)), ("transformer.norm.bias", (D,))]
     for i in reversed(range(cfg.num_layers)):
         specs += layer_param_specs(cfg, i)
-    specs += [("embedding.weight", (D, 3, P, P)), ("embedding.bias", (D,)),
+    specs += [("embedding.weight", (D, 3, *cfg.patch_hw)), ("embedding.bias", (D,)),
               ("transformer.pos_embedding.pos_embedding", (1, cfg.tokens, D)), ("cls_token", (1, 1, D))]
     return specs
 
@@ -439,8 +474,8 @@ class ViTEngine:
         dropout_p > 0: training-mode nn.Dropout(p) at the reference's four sites per model
         (position embedding; per layer the attention output, GELU output and fc2 output)."""
         cfg = self.cfg
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != cfg.image_size or x.shape[3] != cfg.image_size:
-            raise ValueError(f"expected input [b, 3, {cfg.image_size}, {cfg.image_size}], got {tuple(x.shape)}")
+        if x.dim() != 4 or x.shape[1] != 3 or tuple(x.shape[2:]) != cfg.image_hw:
+            raise ValueError(f"expected input [b, 3, {cfg.image_hw[0]}, {cfg.image_hw[1]}], got {tuple(x.shape)}")
         x = x.to(self.dev, torch.float32).contiguous()
         b = x.shape[0]
         a = self.acts(b)
@@ -458,7 +493,7 @@ class ViTEngine:
             self._drop = None
         dd = self._dd
         # patch embedding: im2col + GEMM with conv-bias / cls / pos-emb epilogue
-        ops.im2col(x, a.patches, b, cfg.image_size, cfg.patch_size, a.kpad)
+        ops.im2col_hw(x, a.patches, b, *cfg.image_hw, *cfg.patch_hw, a.kpad)
         wconv = self.wconv if self.wconv is not None else mv[self.off("embedding.weight"):]
         ops.gemm(a.patches, wconv, a.h[0], T, D, a.kpad, a_layout=K_CONTIG, b_layout=K_CONTIG, lda=a.kpad,
                  ldb=a.kpad, ldc=D, epilogue=EPI_PATCH, bias=f[self.off("embedding.bias"):],
@@ -561,8 +596,8 @@ class ViTEngine:
         rounding anywhere. Forward only (logits-parity gate, fp32 evaluation); keeps no activations.
         x: [b, 3, img, img] -> logits [b, C] f32 (a fresh tensor)."""
         cfg = self.cfg
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != cfg.image_size or x.shape[3] != cfg.image_size:
-            raise ValueError(f"expected input [b, 3, {cfg.image_size}, {cfg.image_size}], got {tuple(x.shape)}")
+        if x.dim() != 4 or x.shape[1] != 3 or tuple(x.shape[2:]) != cfg.image_hw:
+            raise ValueError(f"expected input [b, 3, {cfg.image_hw[0]}, {cfg.image_hw[1]}], got {tuple(x.shape)}")
         x = x.to(self.dev, torch.float32).contiguous()
         b = x.shape[0]
         D, M, H, N, L, C = cfg.emb_dim, cfg.mlp_dim, cfg.num_heads, cfg.tokens, cfg.num_layers, cfg.num_classes
@@ -572,7 +607,7 @@ class ViTEngine:
         e = lambda *shape: torch.empty(*shape, device=self.dev)
         fv = lambda name: f[self.off(name):]
         patches = e(T, kp)
-        ops.im2col_f32(x, patches, b, cfg.image_size, cfg.patch_size, kp)
+        ops.im2col_hw_f32(x, patches, b, *cfg.image_hw, *cfg.patch_hw, kp)
         h = e(T, D)
         # Conv2d(k = s = P) as patches x W^T (W [D][3 P^2]), then cls row and position embedding
         ops.gemm_f32(T, D, kp, patches, kp, False, fv("embedding.weight"), kp, True, h, D, bias=fv("embedding.bias"))

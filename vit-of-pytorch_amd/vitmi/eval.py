@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 from .config import get_eval_config
-from .train import SyntheticDataLoader, build_model, load_checkpoint, set_seed
+from .train import SyntheticDataLoader, build_model, fit_pos_embedding, load_checkpoint, set_seed
 
 
 def evaluate(model, data_loader, device):
@@ -47,7 +47,7 @@ def main(argv=None):
     device = torch.device("cuda", 0)
     model = build_model(config, device)
     if config.checkpoint_path:
-        state_dict = load_checkpoint(config.checkpoint_path)
+        state_dict = fit_pos_embedding(load_checkpoint(config.checkpoint_path), model, config)
         model.load_state_dict(state_dict)
         print("Load pretrained weights from {}".format(config.checkpoint_path))
     model = model.to(device)

@@ -402,22 +402,22 @@ def attention_ragged(q, k, v, cu_q, max_q):
 
 
 def patch_embed(x, weight, bias, patch):
-    """nn.Conv2d(3, D, kernel = stride = patch) on images x [B, 3, H, W] as im2col (vit_im2col_f32) + the
-    bf16 MFMA GEMM with bias, returned token-major [B, (H/P)(W/P), D] (the reference's
+    """nn.Conv2d(3, D, kernel = stride = patch) on images x [B, 3, H, W] as im2col (vit_im2col_hw_f32) + the
+    bf16 MFMA GEMM with bias, returned token-major [B, (H/fh)(W/fw), D] (the reference's
     rearrange(conv(x), 'b c h w -> b (h w) c'); res-vit/model.py:629-630, src/model.py:197-200).
-    Gradients reach weight and bias (the images are inputs)."""
+    patch: an int (square) or an (fh, fw) pair. Gradients reach weight and bias (the images are inputs)."""
     _gpu(x, weight, bias)
     if x.requires_grad:
         raise NotImplementedError("patch_embed: no gradient with respect to the input images")
     b, c, hh, ww = x.shape
-    if c != 3 or hh != ww:
-        raise ValueError(f"patch_embed expects square 3-channel images, got {tuple(x.shape)}")
-    g = hh // patch
-    n = g * g
-    k = 3 * patch * patch
+    if c != 3:
+        raise ValueError(f"patch_embed expects 3-channel images, got {tuple(x.shape)}")
+    fh, fw = (patch, patch) if isinstance(patch, int) else patch
+    n = (hh // fh) * (ww // fw)
+    k = 3 * fh * fw
     kpad = _rup(k, 64)
     cols = torch.empty(b * (n + 1), kpad, device=x.device, dtype=F32)
-    ops.im2col_f32(_f32(x), cols, b, hh, patch, kpad)
+    ops.im2col_hw_f32(_f32(x), cols, b, hh, ww, fh, fw, kpad)
     rows = cols.view(b, n + 1, kpad)[:, 1:, :k].reshape(b * n, k)  # drop the cls rows im2col leaves zero
     d = weight.shape[0]
     y = HipLinear.apply(rows, weight.reshape(d, k), bias, False)

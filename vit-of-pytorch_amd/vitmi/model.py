@@ -222,8 +222,6 @@ class VisionTransformer(nn.Module):
         super().__init__()
         h, w = image_size
         fh, fw = patch_size
-        if h != w or fh != fw:
-            raise NotImplementedError("vitmi supports square images and patches")
         gh, gw = h // fh, w // fw
         num_patches = gh * gw
         self.embedding = nn.Conv2d(3, emb_dim, kernel_size=(fh, fw), stride=(fh, fw))
@@ -232,7 +230,9 @@ class VisionTransformer(nn.Module):
                                    num_heads=num_heads, dropout_rate=dropout_rate,
                                    attn_dropout_rate=attn_dropout_rate)
         self.classifier = Linear(emb_dim, num_classes)
-        self.arch = ArchConfig(image_size=h, patch_size=fh, emb_dim=emb_dim, mlp_dim=mlp_dim, num_heads=num_heads,
+        square = h == w and fh == fw  # square models keep the int configs they always built
+        self.arch = ArchConfig(image_size=h if square else (h, w), patch_size=fh if square else (fh, fw),
+                               emb_dim=emb_dim, mlp_dim=mlp_dim, num_heads=num_heads,
                                num_layers=num_layers, num_classes=num_classes)
         self.dropout_rate = dropout_rate
         self.attn_dropout_rate = attn_dropout_rate

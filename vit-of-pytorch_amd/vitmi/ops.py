@@ -206,6 +206,13 @@ def im2col(x, out, B, img, P, Kpad):
     check(lib().vit_im2col(_p(x), _p(out), B, img, P, Kpad, _stream()), "vit_im2col")
 
 
+def im2col_hw(x, out, B, H, W, Ph, Pw, Kpad):
+    """vit_im2col_hw: x f32 [B,3,H,W] -> out bf16 [B * ((H//Ph) * (W//Pw) + 1), Kpad]"""
+    _chk(x, F32, "x")
+    _chk(out, BF16, "out")
+    check(lib().vit_im2col_hw(_p(x), _p(out), B, H, W, Ph, Pw, Kpad, _stream()), "vit_im2col_hw")
+
+
 def preprocess_u8(images, out, flips=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)):
     """images uint8 [B, H, W, 3] (device, image rows contiguous) -> out f32 [B, 3, h, w]:
     Pillow-exact bilinear resize, optional per-sample horizontal flip, ToTensor + Normalize."""
@@ -323,6 +330,12 @@ def im2col_f32(x, out, B, img, P, Kpad):
     _chk(x, F32, "x")
     _chk(out, F32, "out")
     check(lib().vit_im2col_f32(_p(x), _p(out), B, img, P, Kpad, _stream()), "vit_im2col_f32")
+
+
+def im2col_hw_f32(x, out, B, H, W, Ph, Pw, Kpad):
+    _chk(x, F32, "x")
+    _chk(out, F32, "out")
+    check(lib().vit_im2col_hw_f32(_p(x), _p(out), B, H, W, Ph, Pw, Kpad, _stream()), "vit_im2col_hw_f32")
 
 
 def embed_fwd_f32(h, B, N, D, pos, cls):

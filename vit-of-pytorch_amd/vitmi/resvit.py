@@ -592,10 +592,8 @@ class Transformer(nn.Module):
         self.device = params.device
         h, w = params.image_size
         fh, fw = params.patch_size
-        if h != w or fh != fw:
-            raise NotImplementedError("vitmi Res-ViT supports square images and patches")
         params.num_patches = (h // fh) * (w // fw)
-        self.patch = fh
+        self.patch = fh if fh == fw else (fh, fw)
         self.embedding = nn.Conv2d(3, params.dim, kernel_size=(fh, fw), stride=(fh, fw))
         self.cls_token = nn.Parameter(torch.zeros(1, 1, params.dim))
         self.pos_embedding = PositionEmbs(params.num_patches, params.dim)
@@ -619,7 +617,7 @@ class Transformer(nn.Module):
             self.LRA_mask = get_indices_from_LRA_mask(params.block_size)
 
     def embed(self, x):
-        """patch embedding Conv2d(k = s = P) as im2col + the bf16 MFMA GEMM, token-major [B, n, D]."""
+        """patch embedding Conv2d(k = s = patch) as im2col + the bf16 MFMA GEMM, token-major [B, n, D]."""
         return HF.patch_embed(x, self.embedding.weight, self.embedding.bias, self.patch)
 
     def forward(self, x: torch.Tensor, labels: torch.Tensor):

@@ -418,16 +418,16 @@ class _EmbedTokens(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, cls, pos, patch):
-        B, _, hh, _ = x.shape
-        g = hh // patch
-        N = g * g + 1
-        K = 3 * patch * patch
+        B, _, hh, ww = x.shape
+        fh, fw = (patch, patch) if isinstance(patch, int) else patch
+        N = (hh // fh) * (ww // fw) + 1
+        K = 3 * fh * fw
         kpad = _rup(K, 64)
         D = w.shape[0]
         T = B * N
         dev = x.device
         cols = torch.empty(T, kpad, device=dev, dtype=BF16)
-        ops.im2col(x.detach().float().contiguous(), cols, B, hh, patch, kpad)
+        ops.im2col_hw(x.detach().float().contiguous(), cols, B, hh, ww, fh, fw, kpad)
         (wb,) = _pad_bf16_many([(w.detach().float().reshape(D, K).contiguous(), D, kpad)])
         out = torch.empty(B, N, D, device=dev, dtype=F32)
         ops.gemm(cols, wb, out, T, D, kpad, a_layout=K_CONTIG, b_layout=K_CONTIG, lda=kpad, ldb=kpad, ldc=D,
@@ -451,21 +451,23 @@ class _EmbedTokens(torch.autograd.Function):
 
 
 def embed_supported(model, x):
-    """the LoRA configuration's embedding: conv weight / bias and position embeddings frozen, square images of a
-    whole number of patches, as many tokens as position embeddings"""
+    """the LoRA configuration's embedding: conv weight / bias and position embeddings frozen, images of a whole
+    number of patches, as many tokens as position embeddings"""
     e, pe = model.embedding, model.pos_embedding.pos_embedding
-    if not (x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3] and e.bias is not None):
+    if not (x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and e.bias is not None):
         return False
     if e.weight.requires_grad or e.bias.requires_grad or pe.requires_grad or x.requires_grad:
         return False
-    g = x.shape[2] // model.patch
-    return x.shape[2] % model.patch == 0 and pe.shape[1] == g * g + 1 and pe.shape[2] == e.weight.shape[0]
+    fh, fw = (model.patch, model.patch) if isinstance(model.patch, int) else model.patch
+    hh, ww = x.shape[2], x.shape[3]
+    return (hh % fh == 0 and ww % fw == 0 and pe.shape[1] == (hh // fh) * (ww // fw) + 1
+            and pe.shape[2] == e.weight.shape[0])
 
 
 def embed_tokens(model, x):
     """[B, N, D] f32 token rows (cls + patches, position embeddings added) as one node (_EmbedTokens)"""
     return _EmbedTokens.apply(x, model.embedding.weight, model.embedding.bias, model.cls_token,
-                              model.pos_embedding.pos_embedding, int(model.patch))
+                              model.pos_embedding.pos_embedding, model.patch)
 
 
 class _ClsDistill(torch.autograd.Function):

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from . import resvit
 from .optim import AdamW, clip_grad_norm_, get_cosine_schedule_with_warmup
-from .config import process_config
+from .config import _check_image_size, _image_size, image_hw, process_config
 from .flat import sinks as _flat_sinks
 from .train import MetricTracker, StepWriter, SyntheticDataLoader, _rank_mean, rank_batch, set_seed
 
@@ -256,7 +256,7 @@ def get_num_classes_for_dataset(name):
 def config_to_model_args(config):
     """res-vit/config.py:68-96"""
     a = resvit.ModelArgs()
-    a.image_size = (config.image_size, config.image_size)
+    a.image_size = image_hw(config.image_size)
     a.patch_size = (config.patch_size, config.patch_size)
     for k in ("n_heads", "n_kv_heads", "norm_eps", "lora_rank", "dynamic_active_target", "dynamic_start_layer",
               "dynamic_router_hdim", "dynamic_reserve_initials", "low_rank_dim", "block_size", "use_lora",
@@ -274,7 +274,8 @@ def get_train_config(argv=None):
     a("--swanlab", default=True, action="store_true")
     a("--model-arch", type=str, default="b16", choices=["b16", "b32", "l16", "l32", "h14"])
     a("--checkpoint-path", type=str, default="../weights/pytorch/imagenet21k+imagenet2012_ViT-B_16-224.pth")
-    a("--image-size", type=int, default=224, choices=[224, 384])
+    a("--image-size", type=_image_size, default=224, help="224 or 384; any int, or HxW, with --any-image-size")
+    a("--any-image-size", default=False, action="store_true", help="allow any --image-size")
     a("--num-workers", type=int, default=1)
     a("--data-dir", type=str, default="../data/")
     a("--dataset", type=str, default="CIFAR100", choices=["CIFAR10", "CIFAR100", "ImageNet", "TinyImageNet"])
@@ -316,6 +317,7 @@ def get_train_config(argv=None):
     a("--n-gpu", type=int, default=1, help="data-parallel ranks (one per GPU)")
     a("--fused-clip", default=False, action="store_true", help="fold clip_grad_norm_ into the AdamW update")
     config = p.parse_args(argv)
+    _check_image_size(config)
     config.num_classes = get_num_classes_for_dataset(config.dataset)
     return config
 

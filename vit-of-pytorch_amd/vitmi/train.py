@@ -35,7 +35,7 @@ import torch
 import torch.distributed as dist
 
 from . import checkpoint as _ckpt
-from .config import get_train_config
+from .config import get_train_config, image_hw
 from .dist import GradAllReducer
 from .model import CrossEntropyLoss, VisionTransformer
 from .optim import SGD
@@ -160,7 +160,7 @@ class SyntheticDataLoader:
     def __init__(self, batch_size, image_size, num_classes, steps, device, seed=0):
         self.batch_size, self.image_size, self.num_classes, self.steps = batch_size, image_size, num_classes, steps
         g = torch.Generator(device=device).manual_seed(seed)
-        self.x = torch.randn(batch_size, 3, image_size, image_size, device=device, generator=g)
+        self.x = torch.randn(batch_size, 3, *image_hw(image_size), device=device, generator=g)
         self.y = torch.randint(0, num_classes, (batch_size,), device=device, generator=g)
 
     def __len__(self):
@@ -278,8 +278,19 @@ def load_checkpoint(path):
     return _ckpt.load_checkpoint(path)
 
 
+def fit_pos_embedding(state_dict, model, config):
+    """--resize-pos-embedding: the checkpoint's position table resampled to the model's patch grid when they differ"""
+    if not getattr(config, "resize_pos_embedding", False):
+        return state_dict
+    key = _ckpt.POS_EMBEDDING_KEY
+    if key not in state_dict or state_dict[key].shape[1] == model.arch.tokens:
+        return state_dict
+    print("resize position embeddings: {} -> {} tokens".format(state_dict[key].shape[1], model.arch.tokens))
+    return _ckpt.resize_pos_embedding(state_dict, model.arch.grid_hw, key=key)
+
+
 def build_model(config, device):
-    return VisionTransformer(image_size=(config.image_size, config.image_size),
+    return VisionTransformer(image_size=image_hw(config.image_size),
                              patch_size=(config.patch_size, config.patch_size), emb_dim=config.emb_dim,
                              mlp_dim=config.mlp_dim, num_heads=config.num_heads, num_layers=config.num_layers,
                              num_classes=config.num_classes, attn_dropout_rate=config.attn_dropout_rate,
@@ -348,7 +359,7 @@ def main(argv=None):
 
     model = build_model(config, device)
     if config.checkpoint_path:
-        state_dict = load_checkpoint(config.checkpoint_path)
+        state_dict = fit_pos_embedding(load_checkpoint(config.checkpoint_path), model, config)
         if config.num_classes != state_dict["classifier.weight"].size(0):
             del state_dict["classifier.weight"]
             del state_dict["classifier.bias"]
