@@ -6,6 +6,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import attn_ref
 from vitmi import ops
 from vitmi._lib import (EPI_BF16, EPI_BIAS_BF16, EPI_BIAS_GELU, EPI_BIAS_GELU_DGELU, EPI_BIAS_RESID_F32, EPI_F32,
                         EPI_GELU_BWD, EPI_MUL_BF16, EPI_PATCH, EPI_SPLITK, K_CONTIG, MN_CONTIG)
@@ -424,6 +425,97 @@ def test_layernorm(D):
     assert rel(dgb[D:], gb) < 1e-4
 
 
+def _row_ratio(got, ref):
+    """per-row norm ratio, the worst row; floored so that a tiny reference row cannot blow it up"""
+    ref = ref.double()
+    floor = 1e-6 * math.sqrt(ref.shape[1]) * float(ref.abs().max())
+    return float(((got.double() - ref).norm(dim=1) / (ref.norm(dim=1) + floor)).max())
+
+
+@pytest.mark.parametrize("rows,D,dy_f32,y_f32,pad,use_dres", [
+    (4101, 64, False, False, True, True),      # guarded, one chunk per lane
+    (4101, 384, True, True, True, False),      # guarded (FULL = false) with two chunks per lane
+    (4101, 768, False, False, False, True),    # FULL, NV = 3: the production shape's loop
+    (2049, 100, False, True, True, True),      # D % 8 == 4: dgamma | dbeta and the dx column sum by two vit_colsum
+    (5, 2048, True, False, True, False)])      # FULL, NV = 8; fewer rows than one block's waves plus one
+def test_layernorm_rows_and_forms(rows, D, dy_f32, y_f32, pad, use_dres):
+    """The loops production runs, against float64 and per row: more rows than the backward's 512 blocks x 4 waves
+    (4101 = 2 x 2048 + 5: waves walk three rows or two, the software-pipelined prefetch of the next row runs and
+    its `row + stride < rows` guard takes both outcomes), and every form of the ABI: dy / y in bf16 and f32,
+    every stride larger than D (inputs' padding columns hold NaN and must not be read, outputs' must stay
+    untouched), dres absent, accumulate onto non-zero parameter gradients, and the partials-only call, whose
+    block partials reduced afterwards give the fused call's results bit for bit."""
+    g = torch.Generator(device=DEV).manual_seed(rows + D)
+    lds = [D + 4 * k if pad else D for k in range(1, 7)]
+    ldx, ldy, lddy, lddres, lddx, lddxb = lds
+
+    def padded(t, ld, dtype=torch.float32):
+        buf = torch.full((rows, ld), float("nan"), device=DEV, dtype=dtype)
+        buf[:, :D] = t
+        return buf
+
+    def untouched(buf):
+        return bool(torch.isnan(buf[:, D:].float()).all()) and not bool(torch.isnan(buf[:, :D].float()).any())
+
+    x = padded(torch.randn(rows, D, device=DEV, generator=g) * 3 + 1, ldx)
+    gam, bet = torch.randn(D, device=DEV, generator=g), torch.randn(D, device=DEV, generator=g)
+    dy = padded(torch.randn(rows, D, device=DEV, generator=g), lddy, torch.float32 if dy_f32 else torch.bfloat16)
+    dres = padded(torch.randn(rows, D, device=DEV, generator=g), lddres) if use_dres else None
+
+    x64, dy64 = x[:, :D].double(), dy[:, :D].double()
+    mu = x64.mean(1, keepdim=True)
+    rs = 1.0 / torch.sqrt(x64.var(1, unbiased=False, keepdim=True) + 1e-5)
+    xh = (x64 - mu) * rs
+    yref = xh * gam.double() + bet.double()
+    gg = dy64 * gam.double()
+    dxref = rs * (gg - gg.mean(1, keepdim=True) - xh * (gg * xh).mean(1, keepdim=True))
+    if use_dres:
+        dxref = dxref + dres[:, :D].double()
+    dgref, dbref, dsref = (dy64 * xh).sum(0), dy64.sum(0), dxref.sum(0)
+
+    y = torch.full((rows, ldy), float("nan"), device=DEV, dtype=torch.float32 if y_f32 else torch.bfloat16)
+    mean, rstd = torch.full((rows,), float("nan"), device=DEV), torch.full((rows,), float("nan"), device=DEV)
+    ops.layernorm_fwd(x, ldx, gam, bet, y, ldy, mean, rstd, rows, D)
+    assert untouched(y)
+    assert _row_ratio(y[:, :D], yref) < (1e-4 if y_f32 else 5e-3)
+    for got, ref in ((mean, mu[:, 0]), (rstd, rs[:, 0])):
+        assert bool(((got.double() - ref).abs() <= 1e-5 * ref.abs().clamp_min(1.0)).all())
+
+    def backward(dgb, dsum, accumulate=False):
+        dx = torch.full((rows, lddx), float("nan"), device=DEV)
+        dxb = torch.full((rows, lddxb), float("nan"), device=DEV, dtype=torch.bfloat16)
+        part = torch.full((ops.layernorm_bwd_partial_rows(rows), 3 * D), float("nan"), device=DEV)
+        ops.layernorm_bwd(dy, lddy, x, ldx, mean, rstd, gam, dx, lddx, part, rows, D, dres=dres,
+                          lddres=lddres if use_dres else 0, dx_bf16=dxb, lddxb=lddxb, dgamma_dbeta=dgb, dx_colsum=dsum,
+                          accumulate=accumulate)
+        assert untouched(dx) and untouched(dxb)
+        assert _row_ratio(dx[:, :D], dxref) < 1e-4
+        assert _row_ratio(dxb[:, :D], dxref) < 5e-3
+        return dx, dxb, part
+
+    dgb, dsum = torch.full((2 * D,), float("nan"), device=DEV), torch.full((D,), float("nan"), device=DEV)
+    dx, dxb, _ = backward(dgb, dsum)
+    assert rel(dgb[:D], dgref) < 1e-4 and rel(dgb[D:], dbref) < 1e-4 and rel(dsum, dsref) < 1e-4
+
+    # accumulate onto non-zero parameter gradients
+    acc_gb, acc_s = torch.randn(2 * D, device=DEV, generator=g), torch.randn(D, device=DEV, generator=g)
+    init_gb, init_s = acc_gb.double(), acc_s.double()
+    backward(acc_gb, acc_s, accumulate=True)
+    assert rel(acc_gb, init_gb + torch.cat([dgref, dbref])) < 1e-4 and rel(acc_s, init_s + dsref) < 1e-4
+
+    # partials only: the same dx, and the block partials reduce to the fused call's parameter gradients
+    nblk = ops.layernorm_bwd_blocks(rows)
+    dx2, dxb2, part = backward(None, None)
+    assert torch.equal(dx2[:, :D], dx[:, :D]) and torch.equal(dxb2[:, :D], dxb[:, :D])
+    assert not bool(torch.isnan(part[:nblk]).any())
+    psum = part[:nblk].double().sum(0)
+    assert rel(psum[:D], dgref) < 1e-4 and rel(psum[D:2 * D], dbref) < 1e-4 and rel(psum[2 * D:], dsref) < 1e-4
+    if D % 8 == 0:
+        o = [torch.full((D,), float("nan"), device=DEV) for _ in range(3)]
+        ops.colsum3(part, nblk, D, 3 * D, part[nblk:], o[0], o[1], o[2])
+        assert torch.equal(torch.cat(o[:2]), dgb) and torch.equal(o[2], dsum)
+
+
 def _attn_ref(qkv, B, N, H, hd):
     q, k, v = qkv.float().view(B, N, 3, H, hd).permute(2, 0, 3, 1, 4)
     s = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
@@ -469,6 +561,7 @@ def test_attention(B, N, H, hd, path):
     bpart = torch.full((B * rows, 3 * D), float("nan"), device=DEV)
     ops.attention_bwd(qkv.detach(), o, dout, lse, dqkv, B, N, H, hd, 1.0 / math.sqrt(hd), bias_partial=bpart,
                       path=path)
+    bias64 = bpart.view(B, rows, 3 * D).double().sum(1)
     bpart = bpart.view(B, rows, 3 * D).sum(1)
     gref, = torch.autograd.grad(oref, qf, dout.float())
     gq, gk, gv = gref.view(B * N, 3, D).unbind(1)
@@ -480,6 +573,12 @@ def test_attention(B, N, H, hd, path):
     assert rel(mq, gq) < 2e-2
     assert rel(mk, gk) < 2e-2
     assert rel(mv, gv) < 2e-2
+    # per element against float64 (attn_ref.py): a wrong item, slot or row shows by name
+    dq, dk, dv = attn_ref.split_qkv(dqkv, B, N, H, hd)
+    res = attn_ref.check(attn_ref.reference(qkv.detach(), dout, B, N, H, hd, 1.0 / math.sqrt(hd)),
+                         o=attn_ref.split_heads(o, B, N, H, hd), lse=lse, dq=dq, dk=dk, dv=dv,
+                         bias=attn_ref.split_bias(bias64, B, H, hd))
+    assert not attn_ref.failures(res), attn_ref.failures(res)
 
 
 @pytest.mark.parametrize("B,N,H,hd", [(2, 197, 12, 64), (24, 197, 12, 64), (3, 17, 2, 32), (1, 5, 3, 64), (2, 2, 2, 64),
@@ -510,6 +609,9 @@ def test_attention_persistent_forward_matches_oneshot(B, N, H, hd, q_rows):
     if q_rows is None:
         oref, lref = _attn_ref(qkv, B, N, H, hd)
         assert rel(o1.float(), oref) < 1e-2 and rel(l1, lref) < 1e-4
+        res = attn_ref.check(attn_ref.reference(qkv, None, B, N, H, hd, 1.0 / math.sqrt(hd)),
+                             o=attn_ref.split_heads(o1, B, N, H, hd), lse=l1)
+        assert not attn_ref.failures(res), attn_ref.failures(res)
 
 
 @pytest.mark.parametrize("N,B,hd", [(2, 2, 64), (17, 2, 64), (197, 2, 64), (2, 32, 64), (257, 2, 80), (5, 2, 80)])
@@ -692,6 +794,10 @@ def test_attention_fwd_f32():
     ops.attention_fwd_f32(qkv, o, B, N, H, hd, 1.0 / math.sqrt(hd))
     ref, _ = _attn_ref(qkv, B, N, H, hd)
     assert rel(o, ref) < 1e-5
+    # f32 operands, nothing rounded to bf16: per element within f A_o
+    res = attn_ref.check(attn_ref.reference(qkv, None, B, N, H, hd, 1.0 / math.sqrt(hd)), o_factor=attn_ref.F,
+                         o=attn_ref.split_heads(o, B, N, H, hd))
+    assert not attn_ref.failures(res), attn_ref.failures(res)
 
 
 @pytest.mark.parametrize("epi,K", [(EPI_BF16, 64), (EPI_BIAS_RESID_F32, 2048)])
@@ -769,6 +875,9 @@ def test_attention_varlen_ragged_queries(counts, Nkv, H, hd):
         vb = v[b * Nkv:(b + 1) * Nkv].float().view(Nkv, H, hd).transpose(0, 1)
         ref = (torch.softmax(qb @ kb.transpose(-1, -2) / math.sqrt(hd), -1) @ vb).transpose(0, 1).reshape(e - s, D)
         assert rel(o[s:e].float(), ref) < 1e-2, b
+        r, _ = attn_ref.forward_reference(qb, kb, vb, 1.0 / math.sqrt(hd))  # its queries against its Nkv keys
+        res = attn_ref.check(r, o=o[s:e].view(e - s, H, hd).transpose(0, 1))
+        assert not attn_ref.failures(res), (b, attn_ref.failures(res))
 
 
 def test_colsum_batch_exact_integers():
