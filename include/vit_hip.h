@@ -273,6 +273,28 @@ int vit_preprocess_u8(const uint8_t* images, int64_t B, int64_t H, int64_t W, in
                       const uint8_t* flips, int64_t out_h, int64_t out_w, const float* mean_std, float* out,
                       vit_stream_t stream);
 
+/* The same transform fed from a dataset resident in device memory (CIFAR-10/100 as its files store it,
+ * src/data_loaders.py:32-93: dataset -> sampler order -> transform -> batch), fused into one launch:
+ * out[b] = transform(source image index[b]), so a training step's input needs no index_select copy and no
+ * layout change of the set.
+ * images: n_images uint8 images, image i at images + i*image_stride bytes (image_stride >= 3*H*W; the bytes
+ * past 3*H*W of an image are never read). layout VIT_IMAGES_HWC: [H][W][3] interleaved; VIT_IMAGES_CHW: planar
+ * [3][H][W], pixel (c, row, col) at c*H*W + row*W + col (byte loads: no alignment is assumed, W may be odd).
+ * index: device int64 [B], any order, repeats allowed. flips: device uint8 [B], indexed by the OUTPUT image b
+ * (NULL = no flips). Resize, flip and normalisation are vit_preprocess_u8's, bit for bit (the same two kernels:
+ * tiled for <= 9 taps per axis, generic above), out f32 NCHW [B,3,out_h,out_w]; mean_std: host float[6].
+ * labels_in (device int64 [n_images]) and labels_out (device int64 [B]): when both are non-NULL,
+ * labels_out[b] = labels_in[index[b]]; either NULL: labels are not touched.
+ * An index[b] outside [0, n_images) is never read through: out[b] is filled with NaN and labels_out[b] = -1
+ * (vit_cross_entropy's rule for a bad label: the loss of such a step is NaN instead of silently wrong).
+ * images, index, out or mean_std NULL; image_stride < 3*H*W; a layout other than the two; B <= 0, n_images <= 0
+ * or a size <= 0: VIT_ERR_INVALID_ARG, nothing launched. */
+enum vit_image_layout { VIT_IMAGES_HWC = 0, VIT_IMAGES_CHW = 1 };
+int vit_preprocess_u8_gather(const uint8_t* images, int64_t n_images, int32_t layout, int64_t H, int64_t W,
+                             int64_t image_stride, const int64_t* index, int64_t B, const uint8_t* flips,
+                             int64_t out_h, int64_t out_w, const float* mean_std, float* out,
+                             const int64_t* labels_in, int64_t* labels_out, vit_stream_t stream);
+
 /* token-level grads of the embedding (src/model.py:17,203-204): from dh0 f32 [B*N, D]:
  * dpos[n][d] = sum_b dh0[b*N+n][d]; dcls = dpos[0]; dconv_bias = sum_{n>=1} dpos[n].
  * dropout (optional): dh0 is taken through the position-embedding dropout's multipliers first. */

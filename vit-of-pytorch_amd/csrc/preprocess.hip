@@ -8,6 +8,10 @@
 // kernel, which computes each column's and row's weights once per block; larger ratios run the
 // generic kernel (one thread per output pixel, every weight recomputed - deterministically, so the
 // normalising sum and each weight still match Pillow).
+// vit_preprocess_u8_gather is the same transform fed from a resident dataset: output image b reads source
+// image index[b] (HWC or planar CHW, as CIFAR's files store it) and its label travels with it, so a training
+// step's input is one launch with no index_select copy. Both kernels serve both entries; the layouts differ
+// only in Px<LAYOUT>, the pixel fetch.
 #include "common.h"
 
 #include <algorithm>
@@ -71,8 +75,41 @@ struct PrepArgs {
   const uint8_t* flips;
   float mean[3], stdv[3];
   float* out;
+  // gather (vit_preprocess_u8_gather): output image b reads source image index[b]; NULL = image b
+  const int64_t* index;
+  long n_images;
+  const int64_t* labels_in;
+  int64_t* labels_out;
 };
 
+constexpr int kLayoutHWC = 0, kLayoutCHW = 1;
+
+// The pixel fetch, the only per-layout code: channel c of the pixel k columns right of q is q[k * kStep + c * cs].
+// HWC interleaves the channels (step 3, cs 1); planar CHW is plane[c][row * W + col] (step 1, cs H * W). Byte
+// loads only: nothing is assumed about alignment (W may be odd).
+template <int LAYOUT>
+struct Px {
+  static constexpr int kStep = LAYOUT == kLayoutHWC ? 3 : 1;
+  __device__ static inline long chan_stride(const PrepArgs& p) { return LAYOUT == kLayoutHWC ? 1 : (long)p.H * p.W; }
+  __device__ static inline const uint8_t* at(const uint8_t* img, const PrepArgs& p, int row, int col) {
+    return img + ((long)row * p.W + col) * kStep;
+  }
+};
+
+// Source image of output image b: b itself without an index, else index[b], or -1 when that is outside
+// [0, n_images) - such an image is never read through: its output is NaN and its label -1 (the rule
+// vit_cross_entropy has for a bad label).
+__device__ inline long source_image(const PrepArgs& p, int b) {
+  if (!p.index) return b;
+  const long s = p.index[b];
+  return s >= 0 && s < p.n_images ? s : -1;
+}
+
+__device__ inline void gather_label(const PrepArgs& p, int b, long src) {
+  if (p.labels_in && p.labels_out) p.labels_out[b] = src < 0 ? -1 : p.labels_in[src];
+}
+
+template <int LAYOUT>
 __global__ void __launch_bounds__(256) preprocess_kernel(PrepArgs p) {
 #pragma clang fp contract(off)
   const Axis ax = make_axis(p.W, p.ow), ay = make_axis(p.H, p.oh);
@@ -82,21 +119,30 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PrepArgs p) {
     const int b = (int)(i / plane);
     const int rem = (int)(i - (long)b * plane);
     const int y = rem / p.ow, x = rem - y * p.ow;
+    const long srci = source_image(p, b);
+    if (rem == 0) gather_label(p, b, srci);
+    float* o = p.out + (long)b * 3 * plane + rem;
+    if (srci < 0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c * plane] = __builtin_nanf("");
+      continue;
+    }
     const int xs = (p.flips && p.flips[b]) ? p.ow - 1 - x : x;  // the flip mirrors the resized image
     int xmin, xcnt, ymin, ycnt;
     double xc, xw, yc, yw;
     taps(ax, xs, xmin, xcnt, xc, xw);
     taps(ay, y, ymin, ycnt, yc, yw);
-    const uint8_t* img = p.in + (long)b * p.in_bs;
+    const uint8_t* img = p.in + srci * p.in_bs;
+    const long cs = Px<LAYOUT>::chan_stride(p);
     int acc0 = 1 << (kPrecisionBits - 1), acc1 = acc0, acc2 = acc0;
     for (int j = 0; j < ycnt; ++j) {
-      const uint8_t* row = img + ((long)(ymin + j) * p.W + xmin) * 3;
+      const uint8_t* row = Px<LAYOUT>::at(img, p, ymin + j, xmin);
       int h0 = 1 << (kPrecisionBits - 1), h1 = h0, h2 = h0;
       for (int k = 0; k < xcnt; ++k) {
         const int c = coeff(ax, k, xmin, xc, xw);
-        h0 += row[3 * k + 0] * c;
-        h1 += row[3 * k + 1] * c;
-        h2 += row[3 * k + 2] * c;
+        h0 += row[Px<LAYOUT>::kStep * k] * c;
+        h1 += row[Px<LAYOUT>::kStep * k + cs] * c;
+        h2 += row[Px<LAYOUT>::kStep * k + 2 * cs] * c;
       }
       const int cy = coeff(ay, j, ymin, yc, yw);
       acc0 += clip8(h0) * cy;
@@ -104,7 +150,6 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PrepArgs p) {
       acc2 += clip8(h2) * cy;
     }
     const int v[3] = {clip8(acc0), clip8(acc1), clip8(acc2)};
-    float* o = p.out + (long)b * 3 * plane + rem;
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c * plane] = ((float)v[c] / 255.0f - p.mean[c]) / p.stdv[c];
   }
@@ -119,7 +164,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PrepArgs p) {
 // instead of once per output row that uses it.
 constexpr int kColsPerBlock = 64, kRowsPerBlock = 32, kRowLanes = 4, kBandMax = 31 * 4 + 1 + 9;
 
-template <int KMAX>
+template <int KMAX, int LAYOUT>
 __global__ void __launch_bounds__(kColsPerBlock* kRowLanes) preprocess_tiled_kernel(PrepArgs p) {
 #pragma clang fp contract(off)
   __shared__ int s_ky[kRowsPerBlock][KMAX];
@@ -130,6 +175,18 @@ __global__ void __launch_bounds__(kColsPerBlock* kRowLanes) preprocess_tiled_ker
   const int y0 = blockIdx.y * kRowsPerBlock;
   const int rows = p.oh - y0 < kRowsPerBlock ? p.oh - y0 : kRowsPerBlock;
   const int tid = threadIdx.y * kColsPerBlock + threadIdx.x;
+  const long srci = source_image(p, b);  // the same for the whole block
+  if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) gather_label(p, b, srci);
+  if (srci < 0) {
+    const int xo = blockIdx.x * kColsPerBlock + threadIdx.x;
+    if (xo < p.ow) {
+      const long pl = (long)p.oh * p.ow;
+      float* o = p.out + (long)b * 3 * pl + xo;
+      for (int r = threadIdx.y; r < rows; r += kRowLanes)
+        for (int c = 0; c < 3; ++c) o[c * pl + (long)(y0 + r) * p.ow] = __builtin_nanf("");
+    }
+    return;
+  }
   if (tid < rows) {
     int ymin, ycnt;
     double yc, yw;
@@ -153,16 +210,17 @@ __global__ void __launch_bounds__(kColsPerBlock* kRowLanes) preprocess_tiled_ker
   const int band0 = s_ymin[0];
   const int nband = s_ymin[rows - 1] + s_ycnt[rows - 1] - band0;  // <= kBandMax (host: ksize <= 9)
   if (live) {
-    const uint8_t* src = p.in + (long)b * p.in_bs + ((long)band0 * p.W + xmin) * 3;
+    const uint8_t* src = Px<LAYOUT>::at(p.in + srci * p.in_bs, p, band0, xmin);
+    const long cs = Px<LAYOUT>::chan_stride(p);
     for (int r = threadIdx.y; r < nband; r += kRowLanes) {
-      const uint8_t* row = src + (long)r * p.W * 3;
+      const uint8_t* row = src + (long)r * p.W * Px<LAYOUT>::kStep;
       int h0 = 1 << (kPrecisionBits - 1), h1 = h0, h2 = h0;
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         if (k < xcnt) {
-          h0 += row[3 * k + 0] * kx[k];
-          h1 += row[3 * k + 1] * kx[k];
-          h2 += row[3 * k + 2] * kx[k];
+          h0 += row[Px<LAYOUT>::kStep * k] * kx[k];
+          h1 += row[Px<LAYOUT>::kStep * k + cs] * kx[k];
+          h2 += row[Px<LAYOUT>::kStep * k + 2 * cs] * kx[k];
         }
       }
       s_h[r][threadIdx.x] = (uint32_t)clip8(h0) | ((uint32_t)clip8(h1) << 8) | ((uint32_t)clip8(h2) << 16);
@@ -196,6 +254,49 @@ int axis_ksize(long in, long out) {
   return (int)std::ceil(support) * 2 + 1;
 }
 
+// The launch both entries share: the tiled kernel when every axis has at most 9 taps, else the generic one.
+template <int LAYOUT>
+int launch_preprocess(const PrepArgs& p, hipStream_t stream, const char* what) {
+  const int ks = std::max(axis_ksize(p.W, p.ow), axis_ksize(p.H, p.oh));
+  if (ks <= 9 && p.B < 65536) {
+    const dim3 grid((unsigned)((p.ow + kColsPerBlock - 1) / kColsPerBlock),
+                    (unsigned)((p.oh + kRowsPerBlock - 1) / kRowsPerBlock), (unsigned)p.B);
+    const dim3 block(kColsPerBlock, kRowLanes);
+    if (ks <= 3)
+      hipLaunchKernelGGL((preprocess_tiled_kernel<3, LAYOUT>), grid, block, 0, stream, p);
+    else if (ks <= 5)
+      hipLaunchKernelGGL((preprocess_tiled_kernel<5, LAYOUT>), grid, block, 0, stream, p);
+    else
+      hipLaunchKernelGGL((preprocess_tiled_kernel<9, LAYOUT>), grid, block, 0, stream, p);
+    VIT_LAUNCH_CHECK(what);
+  }
+  // generic path: any ratio, every weight recomputed per pixel
+  const long total = (long)p.B * p.oh * p.ow;
+  long blocks = (total + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(preprocess_kernel<LAYOUT>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  VIT_LAUNCH_CHECK(what);
+}
+
+PrepArgs make_args(const uint8_t* images, int64_t B, int64_t H, int64_t W, int64_t image_stride, const uint8_t* flips,
+                   int64_t out_h, int64_t out_w, const float* mean_std, float* out) {
+  PrepArgs p;
+  p.in = images;
+  p.in_bs = image_stride;
+  p.H = (int)H; p.W = (int)W; p.oh = (int)out_h; p.ow = (int)out_w; p.B = (int)B;
+  p.flips = flips;
+  for (int c = 0; c < 3; ++c) {
+    p.mean[c] = mean_std[c];
+    p.stdv[c] = mean_std[3 + c];
+  }
+  p.out = out;
+  p.index = nullptr;
+  p.n_images = B;
+  p.labels_in = nullptr;
+  p.labels_out = nullptr;
+  return p;
+}
+
 }  // namespace
 
 extern "C" int vit_preprocess_u8(const uint8_t* images, int64_t B, int64_t H, int64_t W, int64_t image_stride,
@@ -207,33 +308,29 @@ extern "C" int vit_preprocess_u8(const uint8_t* images, int64_t B, int64_t H, in
   VIT_CHECK_ARG(H < (1 << 15) && W < (1 << 15) && out_h < (1 << 15) && out_w < (1 << 15) &&
                     B * out_h * out_w < (1LL << 40),
                 "vit_preprocess_u8: sizes too large");
-  PrepArgs p;
-  p.in = images;
-  p.in_bs = image_stride;
-  p.H = (int)H; p.W = (int)W; p.oh = (int)out_h; p.ow = (int)out_w; p.B = (int)B;
-  p.flips = flips;
-  for (int c = 0; c < 3; ++c) {
-    p.mean[c] = mean_std[c];
-    p.stdv[c] = mean_std[3 + c];
-  }
-  p.out = out;
-  const int ks = std::max(axis_ksize(W, out_w), axis_ksize(H, out_h));
-  if (ks <= 9 && B < 65536) {
-    const dim3 grid((unsigned)((out_w + kColsPerBlock - 1) / kColsPerBlock),
-                    (unsigned)((out_h + kRowsPerBlock - 1) / kRowsPerBlock), (unsigned)B);
-    const dim3 block(kColsPerBlock, kRowLanes);
-    if (ks <= 3)
-      hipLaunchKernelGGL(preprocess_tiled_kernel<3>, grid, block, 0, (hipStream_t)stream, p);
-    else if (ks <= 5)
-      hipLaunchKernelGGL(preprocess_tiled_kernel<5>, grid, block, 0, (hipStream_t)stream, p);
-    else
-      hipLaunchKernelGGL(preprocess_tiled_kernel<9>, grid, block, 0, (hipStream_t)stream, p);
-    VIT_LAUNCH_CHECK("vit_preprocess_u8");
-  }
-  // generic path: any ratio, every weight recomputed per pixel
-  const long total = B * out_h * out_w;
-  long blocks = (total + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-  VIT_LAUNCH_CHECK("vit_preprocess_u8");
+  const PrepArgs p = make_args(images, B, H, W, image_stride, flips, out_h, out_w, mean_std, out);
+  return launch_preprocess<kLayoutHWC>(p, (hipStream_t)stream, "vit_preprocess_u8");
+}
+
+extern "C" int vit_preprocess_u8_gather(const uint8_t* images, int64_t n_images, int32_t layout, int64_t H, int64_t W,
+                                        int64_t image_stride, const int64_t* index, int64_t B, const uint8_t* flips,
+                                        int64_t out_h, int64_t out_w, const float* mean_std, float* out,
+                                        const int64_t* labels_in, int64_t* labels_out, vit_stream_t stream) {
+  VIT_CHECK_ARG(images && index && out && mean_std, "vit_preprocess_u8_gather: null images / index / out / mean_std");
+  VIT_CHECK_ARG(B > 0 && n_images > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0,
+                "vit_preprocess_u8_gather: B, n_images and every size must be positive");
+  VIT_CHECK_ARG(layout == kLayoutHWC || layout == kLayoutCHW, "vit_preprocess_u8_gather: layout %d (0 = HWC, 1 = CHW)",
+                (int)layout);
+  VIT_CHECK_ARG(H < (1 << 15) && W < (1 << 15) && out_h < (1 << 15) && out_w < (1 << 15) && B < (1LL << 31) &&
+                    B * out_h * out_w < (1LL << 40) && n_images < (1LL << 40),
+                "vit_preprocess_u8_gather: sizes too large");
+  VIT_CHECK_ARG(image_stride >= H * W * 3 && image_stride < (1LL << 40),
+                "vit_preprocess_u8_gather: image_stride %lld < H*W*3", (long long)image_stride);
+  PrepArgs p = make_args(images, B, H, W, image_stride, flips, out_h, out_w, mean_std, out);
+  p.index = index;
+  p.n_images = n_images;
+  p.labels_in = labels_in;
+  p.labels_out = labels_out;
+  if (layout == kLayoutCHW) return launch_preprocess<kLayoutCHW>(p, (hipStream_t)stream, "vit_preprocess_u8_gather");
+  return launch_preprocess<kLayoutHWC>(p, (hipStream_t)stream, "vit_preprocess_u8_gather");
 }

@@ -13,6 +13,23 @@ src/config.py:57-104). Additions for the MI355X path, all optional:
                          (vitmi.checkpoint.resize_pos_embedding)
   --no-save              do not create experiments/ directories or checkpoints
   --precision            (eval) bf16 MFMA forward (default) or the reference's f32 arithmetic
+
+Without --synthetic, the reference's own commands run on CIFAR read from disk (vitmi.datasets, vitmi.data):
+    python -m vitmi.train --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path w.pth ...
+    python -m vitmi.eval  --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path ft.pth ...
+  --dataset CIFAR10 | CIFAR100 (ImageNet / TinyImageNet need JPEG decoding and are refused with that reason)
+  --data-dir D           the files live under D/<dataset>/ as src/train.py:135 joins it, in either published form:
+                           cifar-10-batches-py/{data_batch_1..5,test_batch}   cifar-100-python/{train,test}
+                           cifar-10-batches-bin/{data_batch_1..5,test_batch}.bin   cifar-100-binary/{train,test}.bin
+                         nothing is downloaded; a missing directory is an error naming the paths tried
+  --num-workers          accepted and unused: the set is resident in HBM and transformed there, one launch per batch
+  --seed                 seeds the sample order, which is the reference's DataLoader(shuffle=True,
+                         generator=manual_seed(seed)) order epoch after epoch, and, through a second generator, the
+                         flips. The flips follow the reference's rule (rand < 0.5 per sample) but not its draws: it
+                         makes them inside its worker processes, whose streams depend on --num-workers
+  --n-gpu k              every rank takes its contiguous slice of each global batch (DataParallel's scatter); a ragged
+                         last global batch is kept for k = 1, split when k divides it, otherwise skipped (one line
+                         says how many images per epoch that leaves out)
 """
 from __future__ import annotations
 
@@ -67,7 +84,8 @@ def get_eval_config(argv=None):
     _add_common(parser, train=False)
     parser.add_argument("--checkpoint-path", type=str, default=None, help="model checkpoint to load weights")
     _image_size_arg(parser, 384)
-    parser.add_argument("--num-workers", type=int, default=8, help="number of workers")
+    parser.add_argument("--num-workers", type=int, default=8,
+                        help="accepted and unused (the dataset is resident in HBM: no host workers)")
     parser.add_argument("--dataset", type=str, default="ImageNet", help="dataset for fine-tunning/evaluation")
     parser.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"],
                         help="bf16 MFMA forward or the reference's f32 arithmetic")
@@ -88,7 +106,8 @@ def get_train_config(argv=None):
                         default="../weights/pytorch/imagenet21k+imagenet2012_ViT-B_16-224.pth",
                         help="model checkpoint to load weights")
     _image_size_arg(parser, 224)
-    parser.add_argument("--num-workers", type=int, default=1, help="number of workers")
+    parser.add_argument("--num-workers", type=int, default=1,
+                        help="accepted and unused (the dataset is resident in HBM: no host workers)")
     parser.add_argument("--train-steps", type=int, default=15000, help="number of training/fine-tunning steps")
     parser.add_argument("--lr", type=float, default=0.03, help="learning rate")
     parser.add_argument("--wd", type=float, default=0.0, help="weight decay")

@@ -9,7 +9,12 @@ Top-1 / top-5 come from the fused cross-entropy kernel's per-row hit counts (vit
 src/utils.py:28-41 semantics) instead of a topk pass. Sequences above 320 tokens (384 px: 577 for
 B/16 and L/16, 730 for H/14) run the K/V-tiled attention kernels. `--precision fp32` evaluates with
 the reference's own f32 arithmetic (vit_gemm_f32 projections, f32 attention).
-Data: torchvision is absent here, so the val split is synthetic (--synthetic), as in vitmi.train.
+Data: `--dataset CIFAR10|CIFAR100 --data-dir D` evaluates the test split read from disk and kept in HBM
+(vitmi.datasets, vitmi.data.ResidentLoader), in file order; `--synthetic` a synthetic split, as in
+vitmi.train. ImageNet (the default --dataset) needs JPEG decoding and is not supported.
+
+    python -m vitmi.eval --model-arch b16 --image-size 224 --dataset CIFAR100 --num-classes 100 \\
+        --data-dir ../data --checkpoint-path ft.pth
 """
 from __future__ import annotations
 
@@ -45,6 +50,12 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("vitmi.eval needs a ROCm GPU (MI355X)")
     device = torch.device("cuda", 0)
+    data_loader = None
+    if not config.synthetic:
+        # the reference's {dataset}DataLoader(split='val') (src/eval.py:44-50): the test split, in file order; read
+        # before the model is built, so that a missing dataset stops the run at once
+        from .data import cifar_loaders
+        data_loader, = cifar_loaders(config, config.batch_size, device, splits=("test",))
     model = build_model(config, device)
     if config.checkpoint_path:
         state_dict = fit_pos_embedding(load_checkpoint(config.checkpoint_path), model, config)
@@ -52,11 +63,9 @@ def main(argv=None):
         print("Load pretrained weights from {}".format(config.checkpoint_path))
     model = model.to(device)
     model.precision = config.precision
-    if not config.synthetic:
-        raise SystemExit("torchvision datasets are not available in this environment; use --synthetic "
-                         "(the input pipeline is outside the MI355X hot path, SURVEY.md §2 row 5)")
-    data_loader = SyntheticDataLoader(config.batch_size, config.image_size, config.num_classes,
-                                      config.steps_per_epoch, device, seed=config.seed)
+    if data_loader is None:
+        data_loader = SyntheticDataLoader(config.batch_size, config.image_size, config.num_classes,
+                                          config.steps_per_epoch, device, seed=config.seed)
     print("Starting evaluation")
     acc1, acc5 = evaluate(model, data_loader, device)
     print("Evaluation of model {:s} on dataset {:s}, Acc@1: {:.4f}, Acc@5: {:.4f}".format(

@@ -232,6 +232,46 @@ def preprocess_u8(images, out, flips=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 
                                   out.shape[2], out.shape[3], ms, _p(out), _stream()), "vit_preprocess_u8")
 
 
+IMAGES_HWC, IMAGES_CHW = 0, 1  # enum vit_image_layout
+
+
+def preprocess_u8_gather(images, index, out, flips=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), layout=IMAGES_HWC,
+                         labels_in=None, labels_out=None, image_stride=None):
+    """out[b] = preprocess_u8's transform of images[index[b]] in one launch (vit_preprocess_u8_gather).
+    images: the resident set, uint8 [n, H, W, 3] (layout IMAGES_HWC) or planar [n, 3, H, W] (IMAGES_CHW), each
+    image contiguous, images n apart by images.stride(0) bytes (or `image_stride`). index int64 [B] and
+    flips uint8 [B] live on the device (views of longer arrays are fine); out f32 [B, 3, h, w].
+    labels_out[b] = labels_in[index[b]] when both are given (int64). An index outside [0, n) gives a NaN
+    image and label -1; the library refuses a stride below 3*H*W, an unknown layout and empty batches."""
+    _chk(images, torch.uint8, "images")
+    _chk(index, torch.int64, "index")
+    _chk(out, F32, "out")
+    _chk(flips, torch.uint8, "flips")
+    _chk(labels_in, torch.int64, "labels_in")
+    _chk(labels_out, torch.int64, "labels_out")
+    chw = layout == IMAGES_CHW
+    if images.dim() != 4 or images.shape[1 if chw else 3] != 3 or out.dim() != 4 or out.shape[1] != 3:
+        raise ValueError(f"preprocess_u8_gather: images {'[n,3,H,W]' if chw else '[n,H,W,3]'} -> out [B,3,h,w], got "
+                         f"{tuple(images.shape)} -> {tuple(out.shape)}")
+    n = images.shape[0]
+    H, W = (images.shape[2], images.shape[3]) if chw else (images.shape[1], images.shape[2])
+    B = out.shape[0]
+    if index.dim() != 1 or index.numel() != B or (flips is not None and flips.numel() != B) or \
+            (labels_out is not None and labels_out.numel() != B) or (labels_in is not None and labels_in.numel() != n):
+        raise ValueError("preprocess_u8_gather: batch mismatch")
+    if n and images[0].stride() != ((H * W, W, 1) if chw else (W * 3, 3, 1)) or not out.is_contiguous():
+        raise ValueError("preprocess_u8_gather: every image must be contiguous and out must be contiguous")
+    for name, t in (("index", index), ("flips", flips), ("labels_in", labels_in), ("labels_out", labels_out)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"preprocess_u8_gather: {name} must be contiguous")
+    if image_stride is None:
+        image_stride = images.stride(0) if n > 1 else H * W * 3
+    ms = (ctypes.c_float * 6)(*[float(v) for v in mean], *[float(v) for v in std])
+    check(lib().vit_preprocess_u8_gather(_p(images), n, int(layout), H, W, int(image_stride), _p(index), B, _p(flips),
+                                         out.shape[2], out.shape[3], ms, _p(out), _p(labels_in), _p(labels_out),
+                                         _stream()), "vit_preprocess_u8_gather")
+
+
 def embed_grad(dh0, B, N, D, dpos, dcls, dconv_bias, dropout=None):
     check(lib().vit_embed_grad(_p(dh0), B, N, D, _p(dpos), _p(dcls), _p(dconv_bias), _dp(dropout), _stream()),
           "vit_embed_grad")

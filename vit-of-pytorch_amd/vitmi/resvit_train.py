@@ -276,7 +276,8 @@ def get_train_config(argv=None):
     a("--checkpoint-path", type=str, default="../weights/pytorch/imagenet21k+imagenet2012_ViT-B_16-224.pth")
     a("--image-size", type=_image_size, default=224, help="224 or 384; any int, or HxW, with --any-image-size")
     a("--any-image-size", default=False, action="store_true", help="allow any --image-size")
-    a("--num-workers", type=int, default=1)
+    a("--num-workers", type=int, default=1,
+      help="accepted and unused (the dataset is resident in HBM: no host workers)")
     a("--data-dir", type=str, default="../data/")
     a("--dataset", type=str, default="CIFAR100", choices=["CIFAR10", "CIFAR100", "ImageNet", "TinyImageNet"])
     a("--patch-size", type=int, default=16)
@@ -365,8 +366,11 @@ def main(argv=None):
     if config.checkpoint_path:
         raise SystemExit("load_pretrained_with_mapping (res-vit/utils.py:158-443) is outside the MI355X path; "
                          "pass --checkpoint-path ''")
+    train_loader = valid_loader = None
     if not config.synthetic:
-        raise SystemExit("torchvision datasets are not available in this environment; use --synthetic")
+        # res-vit/data_loaders.py:32-93 (the ViT driver's CIFAR loaders and transform): read from disk, resident in HBM
+        from .data import cifar_loaders
+        train_loader, valid_loader = cifar_loaders(config, batch, device, world, rank)
     optimizer = AdamW(model.parameters(), lr=config.lr, weight_decay=config.wd, betas=(config.beta1, config.beta2),
                       eps=config.eps, max_grad_norm=1.0 if (config.fused_clip and config.clip_grad_norm) else None)
     reducer = None
@@ -375,10 +379,12 @@ def main(argv=None):
         for p in model.parameters():
             dist.broadcast(p.data, 0)
         reducer = FlatGradAllReducer(optimizer.flat).attach()
-    train_loader = SyntheticDataLoader(batch, config.image_size, config.num_classes, config.steps_per_epoch, device,
-                                       seed=config.seed + rank)
-    valid_loader = SyntheticDataLoader(batch, config.image_size, config.num_classes,
-                                       max(1, config.steps_per_epoch // 10), device, seed=10_000 + config.seed + rank)
+    if train_loader is None:
+        train_loader = SyntheticDataLoader(batch, config.image_size, config.num_classes, config.steps_per_epoch,
+                                           device, seed=config.seed + rank)
+        valid_loader = SyntheticDataLoader(batch, config.image_size, config.num_classes,
+                                           max(1, config.steps_per_epoch // 10), device,
+                                           seed=10_000 + config.seed + rank)
     epochs = config.train_steps // len(train_loader)
     if config.lr_scheduler == "cosine":
         lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer=optimizer, T_max=max(1, epochs),

@@ -1,6 +1,8 @@
 """Training driver, mirroring reference src/train.py on the MI355X HIP engine.
 
     python -m vitmi.train --model-arch b16 --batch-size 256 --synthetic --checkpoint-path "" --no-save
+    python -m vitmi.train --model-arch b16 --batch-size 256 --dataset CIFAR100 --num-classes 100 --data-dir ../data \\
+        --checkpoint-path w.pth                       # the reference's fine-tune: CIFAR from disk, in HBM
     python -m vitmi.train --n-gpu 8 --batch-size 512 ...     # data parallel: starts 8 ranks (RCCL)
     torchrun --nproc-per-node 8 -m vitmi.train --n-gpu 8 ... # the same ranks under an outside launcher
 
@@ -357,6 +359,13 @@ def main(argv=None):
         init_process_group(device=device)
     batch = rank_batch(config.batch_size, world)
 
+    train_loader = valid_loader = None
+    if not config.synthetic:
+        # the reference's {dataset}DataLoader pair (src/train.py:134-147), read from disk and kept in HBM; before the
+        # model, so that a missing dataset stops the run before a checkpoint is loaded
+        from .data import cifar_loaders
+        train_loader, valid_loader = cifar_loaders(config, batch, device, world, rank)
+
     model = build_model(config, device)
     if config.checkpoint_path:
         state_dict = fit_pos_embedding(load_checkpoint(config.checkpoint_path), model, config)
@@ -374,10 +383,7 @@ def main(argv=None):
         dist.broadcast(engine.flat, 0)  # identical replicas
         GradAllReducer(engine).attach()  # the backward returns all-reduced (averaged) gradients
 
-    if not config.synthetic:
-        raise SystemExit("torchvision datasets are not available in this environment; use --synthetic "
-                         "(the input pipeline is outside the MI355X hot path, SURVEY.md §2 row 5)")
-    if config.synthetic_source_size > 0:
+    if config.synthetic and config.synthetic_source_size > 0:
         # uint8 images (CIFAR-shaped when 32) through the device-side reference transform
         g = torch.Generator().manual_seed(config.seed + rank)
         n = batch * config.steps_per_epoch
@@ -385,11 +391,13 @@ def main(argv=None):
                             generator=g, dtype=torch.uint8)
         train_loader = DeviceImageLoader(src, torch.randint(0, config.num_classes, (n,), generator=g),
                                          batch, config.image_size, device, seed=config.seed + rank)
-    else:
+    elif config.synthetic:
         train_loader = SyntheticDataLoader(batch, config.image_size, config.num_classes,
                                            config.steps_per_epoch, device, seed=config.seed + rank)
-    valid_loader = SyntheticDataLoader(batch, config.image_size, config.num_classes,
-                                       max(1, config.steps_per_epoch // 10), device, seed=10_000 + config.seed + rank)
+    if valid_loader is None:
+        valid_loader = SyntheticDataLoader(batch, config.image_size, config.num_classes,
+                                           max(1, config.steps_per_epoch // 10), device,
+                                           seed=10_000 + config.seed + rank)
 
     criterion = CrossEntropyLoss()
     optimizer = SGD(params=model.parameters(), lr=config.lr, weight_decay=config.wd, momentum=0.9, model=model)
