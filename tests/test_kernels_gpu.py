@@ -7,6 +7,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import attn_ref
+from gemm_ref import mats as _mats
 from vitmi import ops
 from vitmi._lib import (EPI_BF16, EPI_BIAS_BF16, EPI_BIAS_GELU, EPI_BIAS_GELU_DGELU, EPI_BIAS_RESID_F32, EPI_F32,
                         EPI_GELU_BWD, EPI_MUL_BF16, EPI_PATCH, EPI_SPLITK, K_CONTIG, MN_CONTIG)
@@ -18,32 +19,6 @@ def rel(a, b):
     a = a.double()
     b = b.double()
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
-def _mats(M, N, K, al, bl, ints=False, gen=None):
-    if ints:
-        A = torch.randint(-4, 5, (M, K), device=DEV).float()
-        B = torch.randint(-4, 5, (K, N), device=DEV).float()
-    else:
-        A = torch.randn(M, K, device=DEV)
-        B = torch.randn(K, N, device=DEV)
-    A = A.bfloat16()
-    B = B.bfloat16()
-    # MN-contiguous operands get their rows padded to a multiple of 8 elements (16 B)
-    pad = lambda n: (n + 7) // 8 * 8
-    if al == K_CONTIG:
-        Am, lda = A.contiguous(), K                                  # [M][K]
-    else:
-        lda = pad(M)
-        Am = torch.zeros(K, lda, device=DEV, dtype=torch.bfloat16)   # [K][lda]
-        Am[:, :M] = A.t()
-    if bl == K_CONTIG:
-        Bm, ldb = B.t().contiguous(), K                              # [N][K]
-    else:
-        ldb = pad(N)
-        Bm = torch.zeros(K, ldb, device=DEV, dtype=torch.bfloat16)   # [K][ldb]
-        Bm[:, :N] = B
-    return A, B, Am, Bm, lda, ldb
 
 
 LAYOUTS = [(K_CONTIG, K_CONTIG), (K_CONTIG, MN_CONTIG), (MN_CONTIG, MN_CONTIG), (MN_CONTIG, K_CONTIG)]

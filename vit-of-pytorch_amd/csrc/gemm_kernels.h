@@ -878,10 +878,16 @@ __global__ void __launch_bounds__(WM* WN * 64, (gemm_min_waves<BM, BN, BK, STAGE
 // slots separated by workgroup barriers. In every slot one group reads the fragments of a 64-deep
 // k-tile from LDS while the other group multiplies the fragments it read in the previous slot, so on
 // each SIMD (one wave of each group) LDS reads and MFMA chains of the two waves alternate instead of
-// serialising. Two LDS k-tile buffers: each group issues its half of the LDS-DMA of k-tile u+1 at
-// the end of its read slot of k-tile u (group 0 in slot 2u, group 1 in slot 2u-1 ... k-tile u-1's
-// buffer, which both groups have finished reading), and it is waited for at the end of slot 2u+1,
-// before group 0 first reads it; raw s_barrier (no vmcnt(0) drain at the barriers in between).
+// serialising. NBUF LDS k-tile buffers, L = NBUF - 1 k-tiles ahead: each group issues its half (its
+// waves' pieces) of the LDS-DMA of a k-tile into a buffer that every wave of BOTH groups has left
+// behind a workgroup barrier. Group 0 issues k-tile u+L at the end of its read slot of k-tile u
+// (slot 2u) into k-tile u-1's buffer, which group 1 read in slot 2u-1. Group 1 issues k-tile u+1+L at
+// the start of its multiply slot of k-tile u (slot 2u+2) into k-tile u's buffer: NOT at the end of its
+// read slot 2u+1, where the other waves of group 1 may still be reading that very buffer (the 16-row
+// pieces a fast wave refilled early reached slower waves as the next k-tile's rows: wrong 16-row /
+// 16-column bands of rows 128..255, seen on cache-resident operands where the DMA lands within a read
+// slot). K-tile u+1 is waited for at the end of slot 2u+1, before group 0 first reads it; raw
+// s_barrier (no vmcnt(0) drain at the barriers in between).
 // Epilogue: wave-private fp32 staging in the then idle LDS (32 rows per pass), 8-column chunks.
 // Outstanding-DMA wait with a runtime count of younger k-tiles (0 .. L-1) and compile-time vmcnt.
 template <int LPT, int L>
@@ -997,7 +1003,11 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(const GemmDev p) {
     stage_tile<BN, BK, BKC, NWAVE>(smem, buf + A_BYTES, rsB, p.ldb, kt0 + t, wave, lane);
   };
   // both operands M/N-contiguous (the weight gradients): asm transpose reads (frag_tr_lane_off)
-  constexpr bool TR_ASM = !AK && !BKC;
+  // (not the PATCH epilogue: its instantiation runs out of VGPRs, and hipcc, which takes an asm's output for
+  // ready when the asm returns, spilled a fragment between its ds_read_b64_tr_b16 and the lgkmcnt(0): rows
+  // 240..255 of every tile were multiplied as garbage. Patch embedding never has M/N-contiguous operands in the
+  // models, so it takes the compiler-tracked reads.)
+  constexpr bool TR_ASM = !AK && !BKC && (EPI & 15) != VIT_EPI_PATCH;
   uint32_t a_lane[FM], b_lane[FN];
   if constexpr (TR_ASM) {
     const uint32_t s0 = (uint32_t)(uintptr_t)LDS_PTR(char, smem);
@@ -1057,8 +1067,9 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(const GemmDev p) {
   asm volatile("" ::: "memory");
 
   // slot s: group g reads k-tile j in slot 2j+g and multiplies it in slot 2j+g+1. After its reads of
-  // k-tile j, a group issues its half of k-tile j+L into the buffer of k-tile j+L-NBUF (group 1: of
-  // k-tile j+1+L into k-tile j's buffer, which group 0 read in slot 2j); at the end of slot 2u+1
+  // k-tile j, group 0 issues its half of k-tile j+L into the buffer of k-tile j-1; group 1 issues its
+  // half of k-tile j+1+L into k-tile j's buffer behind the barrier that ends its read slot (every wave
+  // of the group is then done with that buffer; group 0 read it in slot 2j); at the end of slot 2u+1
   // k-tile u+1 has landed (group 0 reads it in slot 2u+2). The two groups run
   // separate straight-line loops (a slot-role branch inside one loop makes the compiler copy the
   // accumulators at every join).
@@ -1075,11 +1086,14 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(const GemmDev p) {
     __builtin_amdgcn_sched_barrier(0);
   };
   PP_STAMP();
-  // Both groups issue their DMA half at the END of their read slot (after the fragment reads): the
-  // buffer they refill held the k-tile both groups have finished reading. Issued at the start of a
-  // slot instead, group 1's half queued behind group 0's in the same slot and held group 1's MFMAs
-  // back ~1 200 cycles per k-tile (tools/gemm_diag stamps, profiles/r03/wgrad_slots_summary.txt:
-  // split-K fc1 weight gradient 3 780 -> 3 130 cycles per k-tile, step +3.5%).
+  // Group 0 issues its DMA half at the END of its read slot (after the fragment reads): the buffer it
+  // refills held the k-tile both groups finished reading before the last barrier. Group 1 must not do
+  // the same: the buffer it refills is the one its own four waves read in that slot, and nothing orders
+  // one wave's issue behind another wave's reads short of the slot's closing barrier, so its half goes
+  // out right behind that barrier, ahead of its MFMAs. (Issued at the end of the read slot it was
+  // ~1 200 cycles per k-tile faster on the split-K weight gradients, profiles/r03/wgrad_slots_summary.txt,
+  // and wrong whenever the DMA landed before the slowest wave's reads; those GEMMs now run on gemm_pp2,
+  // whose half images make the early issue safe.)
   if (grp == 0) {
     for (int j = 0; j < nk; ++j) {
       mem(j);  // slot 2j
@@ -1097,11 +1111,11 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(const GemmDev p) {
     PP_STAMP();
     for (int j = 0; j < nk - 1; ++j) {
       mem(j);  // slot 2j+1
-      if (j + 1 + L < nk) issue(j + 1 + L);
       PP_STAMP();
-      end_odd(j, L + 1);
+      end_odd(j, L);  // issued so far: k-tiles up to j + L
       PP_STAMP();
-      compute();  // slot 2j+2
+      if (j + 1 + L < nk) issue(j + 1 + L);  // slot 2j+2: every wave of the group has read k-tile j
+      compute();
       end_even();
       PP_STAMP();
     }
