@@ -146,6 +146,21 @@ int vit_gemm_bf16_part(const vit_gemm_args* args, int32_t part, vit_stream_t str
  * partial tiles). Fills the CUs where members alone leave a wave partly empty (the out-projection and q|k|v weight
  * gradients of one layer; the Res-ViT router's four weight gradients) */
 int vit_gemm_splitk_group(const vit_gemm_args* args, int32_t n, vit_stream_t stream);
+/* (ABI 21) The same group for up to VIT_GEMM_TABLE_MAX members, their descriptors kept in a device-memory table
+ * (the weight gradients of a whole backward in one launch). Members are as for vit_gemm_splitk_group; each has its
+ * own K, split_k and batch. A member i with direct[i] != 0 (split_k must be 1) writes no slab: it stores the f32
+ * result itself, C[z*c_batch_stride + m*ldc + n] = acc for m < M, n < N and nothing else, one accumulation chain
+ * over all of K, bit-identical to the member's slab at split_k 1 reduced by vit_splitk_reduce. direct may be NULL.
+ *   vit_gemm_group_table_bytes(n): size of the table (0 for an n outside 1..VIT_GEMM_TABLE_MAX);
+ *   vit_gemm_group_prepare: validates the members and uploads the table (16-byte aligned device memory the caller
+ *     keeps alive); synchronises `stream` first, so a table may be rebuilt in place. Call it when the member list
+ *     changes, not per launch. *total receives the grid size;
+ *   vit_gemm_group_launch: one launch of `total` workgroups over the prepared table. */
+#define VIT_GEMM_TABLE_MAX 128
+int64_t vit_gemm_group_table_bytes(int32_t n);
+int vit_gemm_group_prepare(const vit_gemm_args* args, const int32_t* direct, int32_t n, void* table,
+                           int64_t table_bytes, int32_t* total, vit_stream_t stream);
+int vit_gemm_group_launch(const void* table, int32_t n, int32_t total, vit_stream_t stream);
 
 /* out[z*out_batch_stride + m*ldo + n] (+)= sum_s ws[((z*split + s)*M + m)*N + n]  (f32) */
 int vit_splitk_reduce(const float* ws, int64_t batch, int64_t split, int64_t M, int64_t N,

@@ -17,6 +17,8 @@
 //   * XCD-aware bijective block remap so consecutive tiles (same A rows) share an XCD's L2.
 #include "gemm_decl.h"
 
+#include <vector>
+
 namespace {
 using vitg::GemmDev;
 using vitg::EPI_DROP;
@@ -190,6 +192,10 @@ int make_dev(const vit_gemm_args* a, GemmDev& d, bool& empty) {
     if (a->epilogue == VIT_EPI_SPLITK) v = al(a->C) && a->N % 8 == 0;
     d.vec = v ? 1 : 0;
   }
+  if (a->epilogue == VIT_EPI_SPLITK) {  // packed f32 slabs: the arguments' ldc / c_batch_stride are not used
+    d.ldc = a->N;
+    d.c_bs = a->M * a->N;
+  }
   d.col_partial = a->col_partial;
   d.drop = make_drop(a->dropout);
   VIT_CHECK_ARG(!d.drop.thr || a->epilogue == VIT_EPI_PATCH || a->epilogue == VIT_EPI_BIAS_RESID_F32 ||
@@ -323,6 +329,60 @@ extern "C" int vit_gemm_splitk_group(const vit_gemm_args* args, int32_t n, vit_s
   g.start[n] = (int)total;
   g.n = n;
   return vit::check_hip(vitg::launch_splitk_group(g, (hipStream_t)stream), "vit_gemm_splitk_group launch");
+}
+
+extern "C" int64_t vit_gemm_group_table_bytes(int32_t n) {
+  return n >= 1 && n <= vitg::GEMM_TABLE_MAX ? (int64_t)vitg::group_table_bytes(n) : 0;
+}
+
+extern "C" int vit_gemm_group_prepare(const vit_gemm_args* args, const int32_t* direct, int32_t n, void* table,
+                                      int64_t table_bytes, int32_t* total_out, vit_stream_t stream) {
+  VIT_CHECK_ARG(args != nullptr && n >= 1 && n <= vitg::GEMM_TABLE_MAX, "vit_gemm_group_prepare: 1..%d members, got %d",
+                vitg::GEMM_TABLE_MAX, n);
+  VIT_CHECK_ARG(table != nullptr && total_out != nullptr && table_bytes >= (int64_t)vitg::group_table_bytes(n) &&
+                    ((uintptr_t)table % 16) == 0,
+                "vit_gemm_group_prepare: needs a 16-byte aligned table of vit_gemm_group_table_bytes(n) bytes");
+  const size_t soff = vitg::group_table_start_off(n);
+  std::vector<char> host(vitg::group_table_bytes(n), 0);
+  GemmDev* g = reinterpret_cast<GemmDev*>(host.data());
+  int* start = reinterpret_cast<int*>(host.data() + soff);
+  long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const vit_gemm_args* a = args + i;
+    VIT_CHECK_ARG(a->epilogue == VIT_EPI_SPLITK && a->a_layout == VIT_MN_CONTIG && a->b_layout == VIT_MN_CONTIG &&
+                      a->tile == 0 && !a->col_partial && !a->dropout,
+                  "vit_gemm_group_prepare: member %d must be a split-K weight gradient (VIT_EPI_SPLITK, both operands "
+                  "M/N-contiguous, no tile / col_partial / dropout)", i);
+    bool empty = false;
+    if (const int rc = make_dev(a, g[i], empty)) return rc;
+    VIT_CHECK_ARG(!empty, "vit_gemm_group_prepare: member %d is empty", i);
+    if (direct && direct[i]) {
+      // the f32 result itself, at the caller's strides, instead of a packed slab
+      VIT_CHECK_ARG(a->split_k == 1 && a->ldc >= a->N && (a->batch == 1 || a->c_batch_stride > 0),
+                    "vit_gemm_group_prepare: direct member %d needs split_k 1, ldc >= N and an output batch stride", i);
+      g[i].ldc = a->ldc;
+      g[i].c_bs = a->c_batch_stride;
+      g[i].vec = ((uintptr_t)a->C % 32) == 0 && a->ldc % 8 == 0 && a->c_batch_stride % 8 == 0;
+    }
+    start[i] = (int)total;
+    total += ((a->M + 255) / 256) * ((a->N + 255) / 256) * a->split_k * a->batch;
+    VIT_CHECK_ARG(total < (1L << 30), "vit_gemm_group_prepare: grid too large");
+  }
+  start[n] = (int)total;
+  // rare (once per member list): a synchronous upload, ordered behind the stream's earlier launches of the table
+  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = vit::check_hip(hipStreamSynchronize(s), "vit_gemm_group_prepare sync")) return rc;
+  if (const int rc = vit::check_hip(hipMemcpy(table, host.data(), host.size(), hipMemcpyHostToDevice),
+                                    "vit_gemm_group_prepare upload"))
+    return rc;
+  *total_out = (int32_t)total;
+  return VIT_OK;
+}
+
+extern "C" int vit_gemm_group_launch(const void* table, int32_t n, int32_t total, vit_stream_t stream) {
+  VIT_CHECK_ARG(table != nullptr && n >= 1 && n <= vitg::GEMM_TABLE_MAX && total >= 1,
+                "vit_gemm_group_launch: a prepared table, its member count and its workgroup total");
+  return vit::check_hip(vitg::launch_group_table(table, n, total, (hipStream_t)stream), "vit_gemm_group_launch");
 }
 
 // ---- split-K reduction -------------------------------------------------------------------------

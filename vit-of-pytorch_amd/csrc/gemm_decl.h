@@ -32,8 +32,8 @@ struct GemmDev {
   long b_bs;
   uint32_t b_bytes;
   void* C;
-  long ldc;
-  long c_bs;
+  long ldc;   // (VIT_EPI_SPLITK: the row stride of a slab, N; a direct group member's own output row stride)
+  long c_bs;  // (VIT_EPI_SPLITK: the stride between (batch, split) slabs, M N; a direct member's batch stride)
   void* C2;
   long ldc2;
   const float* bias;
@@ -66,6 +66,13 @@ struct GemmGroup {
   int n;
 };
 hipError_t launch_splitk_group(const GemmGroup& g, hipStream_t s);
+
+// The same group with its members in a device-memory table (vit_gemm_group_prepare / vit_gemm_group_launch): n
+// descriptors followed by n + 1 start positions, so the member count is not bound by the kernel-argument size
+constexpr int GEMM_TABLE_MAX = 128;
+inline size_t group_table_start_off(int n) { return ((size_t)n * sizeof(GemmDev) + 15) & ~(size_t)15; }
+inline size_t group_table_bytes(int n) { return group_table_start_off(n) + ((size_t)n + 1) * sizeof(int); }
+hipError_t launch_group_table(const void* table, int n, int total, hipStream_t s);
 
 // Internal epilogue flag: the dropout variant of PATCH / BIAS_RESID_F32 / BIAS_GELU_DGELU (its own
 // instantiation, so the dropout-free kernels carry none of the Philox code)

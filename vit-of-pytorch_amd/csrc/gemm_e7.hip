@@ -6,3 +6,7 @@ template <> hipError_t vitg::launch_layout_x<7>(int cfg, const GemmDev& d, bool 
 }
 
 hipError_t vitg::launch_splitk_group(const GemmGroup& g, hipStream_t s) { return launch_pp2_group(g, s); }
+
+hipError_t vitg::launch_group_table(const void* table, int n, int total, hipStream_t s) {
+  return launch_pp2_table(table, n, total, s);
+}

@@ -70,7 +70,6 @@ __device__ __forceinline__ void stage_tile(char* smem, int lds_off, __amdgpu_buf
   }
 }
 
-// 16 rows (r0..r0+15) x 32 k (kk*32..) MFMA fragment of this lane.
 // piece i (0 <= i < INSTR) of stage_tile's image alone (gemm_pp2's interleaved read slot). Same addressing as
 // stage_tile, which keeps its own loop so that the lane offset and the row step are computed once per image.
 template <int ROWS, int BK, bool KC, int NWAVE>
@@ -94,6 +93,7 @@ __device__ __forceinline__ void stage_piece(char* smem, int lds_off, __amdgpu_bu
                                            lane_off + base, 0, 0, 0);
 }
 
+// 16 rows (r0..r0+15) x 32 k (kk*32..) MFMA fragment of this lane.
 template <int ROWS, int BK, bool KC>
 __device__ __forceinline__ v8s read_frag(const char* smem, int lds_off, int r0, int kk, int lane) {
   if constexpr (KC) {
@@ -208,8 +208,10 @@ __device__ __forceinline__ void epi_store(const GemmDev& p, int z, int split_idx
     if constexpr (DROP) o *= drop_mult1(p.drop, m, n);
     C[(long)m * p.ldc + n] = o;
   } else if constexpr (E == VIT_EPI_SPLITK) {
-    float* C = (float*)p.C + ((long)z * p.split_k + split_idx) * (long)p.M * p.N;
-    C[(long)m * p.N + n] = v;
+    // slab (z, split) at stride c_bs with row stride ldc: M * N and N for slabs, the caller's own output strides
+    // for a direct member of vit_gemm_group_launch (make_dev / group_prepare set them)
+    float* C = (float*)p.C + ((long)z * p.split_k + split_idx) * p.c_bs;
+    C[(long)m * p.ldc + n] = v;
   }
 }
 
@@ -379,7 +381,7 @@ __device__ __forceinline__ void epi_store8(const GemmDev& p, int z, int split_id
     }
     st8f((float*)p.C + (long)m * p.ldc + n, v, p.nt);
   } else if constexpr (E == VIT_EPI_SPLITK) {
-    st8f((float*)p.C + ((long)z * p.split_k + split_idx) * (long)p.M * p.N + (long)m * p.N + n, v, p.nt);
+    st8f((float*)p.C + ((long)z * p.split_k + split_idx) * p.c_bs + (long)m * p.ldc + n, v, p.nt);
   }
 }
 
@@ -491,7 +493,7 @@ template <int EPI>
 __device__ __forceinline__ void epi_put8(const GemmDev& p, int z, int split_idx, int m, int n, const uint4* o) {
   constexpr int E = EPI & 15;
   if constexpr (E == VIT_EPI_SPLITK) {
-    float* q = (float*)p.C + ((long)z * p.split_k + split_idx) * (long)p.M * p.N + (long)m * p.N + n;
+    float* q = (float*)p.C + ((long)z * p.split_k + split_idx) * p.c_bs + (long)m * p.ldc + n;
     st16(q, o[0], p.nt);
     st16(q + 4, o[1], p.nt);
   } else if constexpr (EpiOut<EPI>::W == 1) {

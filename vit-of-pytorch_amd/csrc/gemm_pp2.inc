@@ -492,6 +492,35 @@ __global__ void __launch_bounds__(512) gemm_pp2_group_kernel(const GemmGroup G) 
   pp2_tile<AK, BKC, VIT_EPI_SPLITK>(p, tm, tn, z, split_idx, orig);
 }
 
+// The group with its members in a device-memory table (any member count; vit_gemm_group_launch): the weight
+// gradients of a whole backward as one grid. Members may differ in K and in split: a member at split 1 whose
+// descriptor carries its output's own strides (c_bs, ldc) writes its gradient directly, one accumulation chain over
+// all of K and no slab. The whole space is XCD-major, members in the caller's order, so one member's tiles (which
+// share its operand panels) are adjacent positions of one XCD. Assumed about dispatch, for speed only: launch
+// indices are dealt to the 8 XCDs in turn and start in order, so in every round an XCD's CUs hold a run of
+// neighbouring positions. No workgroup waits for another; a different dispatch order costs L2 hits, not results.
+template <bool AK, bool BKC>
+__global__ void __launch_bounds__(512) gemm_pp2_table_kernel(const GemmDev* __restrict__ tab,
+                                                             const int* __restrict__ start, const int n) {
+  const int orig = blockIdx.x;
+  const int w = xcd_major(orig, (int)gridDim.x);
+  // wave-uniform binary search (blockIdx only: scalar loads): the last member with start[gi] <= w
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (w >= start[mid])
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const int gi = __builtin_amdgcn_readfirstlane(lo);
+  const GemmDev p = tab[gi];  // a copy in registers: the main loop's "memory" clobbers reload nothing
+  const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
+  int tm, tn, z, split_idx;
+  splitk_coords(p, w - start[gi], tiles_m * tiles_n, tiles_m, tiles_n, tm, tn, z, split_idx);
+  pp2_tile<AK, BKC, VIT_EPI_SPLITK>(p, tm, tn, z, split_idx, orig);
+}
+
 template <bool AK, bool BKC, int EPI, int BK = 64, int NA = 2>
 hipError_t launch_pp2(const GemmDev& d, int batch, int split, hipStream_t s) {
   const int tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256);
@@ -503,5 +532,13 @@ hipError_t launch_pp2(const GemmDev& d, int batch, int split, hipStream_t s) {
 // the split-K group (M/N-contiguous operands: the weight gradients' layout)
 inline hipError_t launch_pp2_group(const GemmGroup& g, hipStream_t s) {
   hipLaunchKernelGGL((gemm_pp2_group_kernel<false, false>), dim3(g.start[g.n]), dim3(512), 0, s, g);
+  return hipGetLastError();
+}
+
+// ... with the members in a device table of n descriptors and n + 1 starts (total = start[n] workgroups)
+inline hipError_t launch_pp2_table(const void* table, int n, int total, hipStream_t s) {
+  const GemmDev* tab = (const GemmDev*)table;
+  const int* start = (const int*)((const char*)table + vitg::group_table_start_off(n));
+  hipLaunchKernelGGL((gemm_pp2_table_kernel<false, false>), dim3(total), dim3(512), 0, s, tab, start, n);
   return hipGetLastError();
 }

@@ -17,7 +17,7 @@ c_i32 = ctypes.c_int32
 c_f32 = ctypes.c_float
 c_vp = ctypes.c_void_p
 
-ABI_VERSION = 20  # vit_abi_version() of the library these prototypes describe
+ABI_VERSION = 21  # vit_abi_version() of the library these prototypes describe
 
 # enum vit_layout / vit_epilogue (include/vit_hip.h)
 K_CONTIG, MN_CONTIG = 0, 1
@@ -82,6 +82,10 @@ _SIGS = {
     "vit_gemm_split_rows": (c_i64, [ctypes.POINTER(GemmArgs)]),
     "vit_gemm_bf16_part": (c_i32, [ctypes.POINTER(GemmArgs), c_i32, c_vp]),
     "vit_gemm_splitk_group": (c_i32, [ctypes.POINTER(GemmArgs), c_i32, c_vp]),
+    "vit_gemm_group_table_bytes": (c_i64, [c_i32]),
+    "vit_gemm_group_prepare": (c_i32, [ctypes.POINTER(GemmArgs), ctypes.POINTER(c_i32), c_i32, c_vp, c_i64,
+                                       ctypes.POINTER(c_i32), c_vp]),
+    "vit_gemm_group_launch": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "vit_segment_colsum": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp, c_i64, c_vp]),
     "vit_segment_colsum_bcast": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp, c_i64,
                                          c_vp, c_i64, c_i64, c_vp]),

@@ -220,6 +220,21 @@ class _Acts:
         self.c_o, self.c_ln2, self.c_dh, self.c_dh2, self.c_dyln = (z(bp, D) for _ in range(5))
         self.c_g, self.c_gp, self.c_dg = (z(bp, M) for _ in range(3))
         self.c_mu2, self.c_rs2 = z(b, dt=f), z(b, dt=f)
+        self._cfg, self._dev = cfg, dev
+        self.dhb_l = self.dg_l = self.dqkv_l = None
+
+    def defer_bufs(self):
+        """Per-layer bf16 gradient operands of the deferred weight gradients (ViTEngine.wgrad_defer): every dhb (two
+        per layer and the embedding's), dg and dq|dk|dv stays intact until the batched launch at the end of the
+        backward. Allocated on first use, the double buffers above are its first entries."""
+        if self.dhb_l is None:
+            cfg = self._cfg
+            D, M, L = cfg.emb_dim, cfg.mlp_dim, cfg.num_layers
+            z = lambda *s: torch.zeros(*s, device=self._dev, dtype=torch.bfloat16)
+            self.dhb_l = self.dhb + [z(self.Tp, D) for _ in range(2 * L - 1)]
+            self.dg_l = self.dg + [z(self.Tp, M) for _ in range(max(L - 2, 0))]
+            self.dqkv_l = self.dqkv + [z(self.Tp, 3 * D) for _ in range(max(L - 2, 0))]
+        return self.dhb_l, self.dg_l, self.dqkv_l
 
 
 class _BiasReducer:
@@ -327,6 +342,14 @@ class ViTEngine:
         # each layer's out-projection and q|k|v weight gradients in one split-K launch (ops.gemm_splitk_group);
         # VITMI_GROUP_WGRAD=0: two launches
         self.group_wgrad = os.environ.get("VITMI_GROUP_WGRAD", "1") != "0"
+        # Deferred weight gradients: the full-token layers only record their weight-gradient GEMMs and every
+        # wgrad_defer layers' worth runs as ONE launch (ops.GemmGroupTable): enough tiles to fill the CUs at split 1,
+        # so each tile is accumulated over all tokens in registers and written once, without slabs or reductions.
+        # Taken only when nothing needs a layer's gradients early (no grad_ready_hook, no overlap_wgrad).
+        # VITMI_WGRAD_DEFER: 0 = the per-layer path, N > 0 = layers per launch, "all" (default) = one launch.
+        v = os.environ.get("VITMI_WGRAD_DEFER", "all")
+        self.wgrad_defer = L if v == "all" else int(v)
+        self._wgrad_tables = {}  # (batch size, launch of the backward, first member) -> (member key, GemmGroupTable)
         # Only the cls token of the last layer's output reaches the classifier (src/model.py:210),
         # so that layer's out-projection, LayerNorm 2 and MLP (forward and backward) run on the b cls
         # rows and its attention on the first 32-query pair of each (image, head) (q_rows = 1); the
@@ -460,6 +483,52 @@ class ViTEngine:
             ev1.record()
             self.probe_wgrad.append((ev0, ev1, sum(2.0 * sp[4] * sp[5] * K * sp[9] for sp in specs), K, True))
         ops.splitk_reduce_group([(w, sp[9], s, sp[4], sp[5], sp[7], sp[8], sp[11], False) for sp, w in zip(specs, views)])
+
+    def _wgrad_batch(self, specs, slot):
+        """Deferred weight gradients (specs as for _wgrad_group, all over the same K) as one launch per
+        ops.GEMM_TABLE_MAX members. At the common split 1 (the usual case: a backward's worth of tiles covers the
+        CUs several times) every member writes its gradient directly; otherwise slabs and their fixed-order
+        reduction as in _wgrad_group. The device table is rebuilt only when the member list changes (engine
+        buffers are persistent: once per batch size); `slot` names this launch within the backward."""
+        K = specs[0][6]
+        assert all(sp[6] == K for sp in specs)
+        s = ops.splitk_factor_group([(sp[4], sp[5], sp[9]) for sp in specs], K, _WGRAD_TARGET)
+        views = None
+        if s > 1:
+            sizes = [sp[9] * s * sp[4] * sp[5] for sp in specs]
+            ws = self._workspace(sum(sizes))
+            views, o = [], 0
+            for n in sizes:
+                views.append(ws[o:o + n])
+                o += n
+        for c0 in range(0, len(specs), ops.GEMM_TABLE_MAX):
+            part = specs[c0:c0 + ops.GEMM_TABLE_MAX]
+            key = (s, self._ws.data_ptr() if s > 1 else 0) + tuple(
+                (sp[0].data_ptr(), sp[1], sp[2].data_ptr(), sp[3], sp[4], sp[5], sp[7].data_ptr()) + tuple(sp[8:])
+                for sp in part)
+            ent = self._wgrad_tables.get((self._last_b, slot, c0))
+            if ent is None or ent[0] != key:
+                members = []
+                for k, (A, lda, B, ldb, M, N, _, out, ldo, batch, b_bs, out_bs) in enumerate(part):
+                    kw = dict(a_layout=MN_CONTIG, b_layout=MN_CONTIG, lda=lda, ldb=ldb, epilogue=EPI_SPLITK, batch=batch,
+                              b_bs=b_bs, split_k=s)
+                    if s == 1:
+                        members.append((A, B, out, M, N, K, dict(kw, ldc=ldo, c_bs=out_bs), True))
+                    else:
+                        members.append((A, B, views[c0 + k], M, N, K, dict(kw, ldc=N), False))
+                ent = (key, ops.GemmGroupTable(members))
+                self._wgrad_tables[(self._last_b, slot, c0)] = ent
+            if self.probe_wgrad is not None:
+                ev0 = torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            ent[1].launch()
+            if self.probe_wgrad is not None:
+                ev1 = torch.cuda.Event(enable_timing=True)
+                ev1.record()
+                self.probe_wgrad.append((ev0, ev1, sum(2.0 * sp[4] * sp[5] * K * sp[9] for sp in part), K, True))
+        if s > 1:
+            ops.splitk_reduce_group([(w, sp[9], s, sp[4], sp[5], sp[7], sp[8], sp[11], False)
+                                     for sp, w in zip(specs, views)])
 
     # ---- forward -------------------------------------------------------------------------------
     def _dd(self, site, row_stride=1):
@@ -651,7 +720,11 @@ class ViTEngine:
         Two streams: the main stream runs the data-gradient chain (dgrad GEMMs, LayerNorm and
         attention backward); the weight-gradient GEMMs, which nothing downstream waits for, run on
         a side stream as soon as their operands exist. bf16 gradient operands are double-buffered
-        and each buffer is recycled only after the side stream has consumed it."""
+        and each buffer is recycled only after the side stream has consumed it.
+
+        Deferred mode (wgrad_defer > 0, no grad_ready_hook, no overlap_wgrad): the full-token layers' weight
+        gradients are only recorded, their operands kept in per-layer buffers (_Acts.defer_bufs), and run as
+        one batched launch per wgrad_defer layers (_wgrad_batch), the last one after the last data gradient."""
         cfg = self.cfg
         b = self._last_b
         a = self.acts(b)
@@ -707,6 +780,18 @@ class ViTEngine:
 
         self._ev_next = 0  # the event pool is reused from the start by every backward
         group = self.group_wgrad and D >= 256  # (the grouped kernel takes M, N >= 256)
+        # deferred weight gradients (wgrad_defer layers per launch), unless something wants a layer's gradients early
+        defer = self.wgrad_defer if not hook and not overlap and D >= 256 and M >= 256 else 0
+        pending, held, launches = [], 0, 0  # recorded specs, layers among them, launches issued
+        dhbs, dgs, dqkvs = a.defer_bufs() if defer else (a.dhb, a.dg, a.dqkv)
+        nd = len(dhbs)
+
+        def flush_wgrad():
+            nonlocal pending, held, launches
+            if pending:
+                self._wgrad_batch(pending, launches)
+                launches += 1
+            pending, held = [], 0
         out_wb = None  # dhb buffer of a deferred out-projection weight gradient (group)
         bias = _BiasReducer(self, a)
         # classifier head (f32): dWc = dl^T lncls, dbc = colsum(dl), dlncls = dl Wc
@@ -719,27 +804,30 @@ class ViTEngine:
         pruned = self._pruned
         ops.zero_(a.dh)
         if not pruned:
-            ops.zero_(a.dhb[wb])
+            ops.zero_(dhbs[wb])
         bias.ln_bwd(a.dlncls, D, a.h[L], N * D, a.muf, a.rsf, f[self.off("transformer.norm.weight"):], a.dh, N * D, b,
                     gv("transformer.norm.weight"), gv(self.lname(L - 1, "mlp.fc2.bias")),
-                    dx_bf16=a.c_dh if pruned else a.dhb[wb], lddxb=D if pruned else N * D,
+                    dx_bf16=a.c_dh if pruned else dhbs[wb], lddxb=D if pruned else N * D,
                     dx_dropout=dd(3 + 3 * (L - 1), N))
         fire(self.layout.buckets[0])
         scale = 1.0 / math.sqrt(hd)
         for i in reversed(range(L)):
             ln = lambda s: self.off(self.lname(i, s))
-            li = i & 1
+            li = i % len(dgs)
             if pruned and i == L - 1:
                 # MLP, LayerNorm 2 and out-projection backward on the cls rows; dO = 0 elsewhere
                 self._backward_last_cls(a, i, b, g, on_side, bias)
-                wb ^= 1
+                wb = (wb + 1) % nd
             else:
-                dhb = a.dhb[wb]
+                dhb = dhbs[wb]
                 # ---- MLP: h_{i+1} = hm + fc2(gelu(fc1(ln2(hm)))) ----
                 # (fc2 bias grad = column sums of dh, already produced by the LayerNorm backward above)
-                on_side(lambda: self._wgrad(dhb, D, a.g[i], M, D, M, a.Tp, gv(self.lname(i, "mlp.fc2.weight")), M))
+                if defer:
+                    pending.append((dhb, D, a.g[i], M, D, M, a.Tp, gv(self.lname(i, "mlp.fc2.weight")), M, 1, 0, 0))
+                else:
+                    on_side(lambda: self._wgrad(dhb, D, a.g[i], M, D, M, a.Tp, gv(self.lname(i, "mlp.fc2.weight")), M))
                 release("dhb", wb)
-                dg = a.dg[li]
+                dg = dgs[li]
                 acquire("dg", li)
                 gpart = bias.buf("gelu", a.gelu_parts)
                 w2 = mv[ln("mlp.fc2.weight"):]
@@ -748,26 +836,31 @@ class ViTEngine:
                 ops.gemm(dhb, w2, dg, T, M, D, **kw)
                 tiles_m = ops.gemm_partial_rows(dhb, w2, dg, T, M, D, **kw)
                 bias.reduce(gpart, tiles_m, M, M, (gv(self.lname(i, "mlp.fc1.bias")),))
-                on_side(lambda: self._wgrad(dg, M, a.ln2[i], D, M, D, a.Tp, gv(self.lname(i, "mlp.fc1.weight")), D))
+                if defer:
+                    pending.append((dg, M, a.ln2[i], D, M, D, a.Tp, gv(self.lname(i, "mlp.fc1.weight")), D, 1, 0, 0))
+                else:
+                    on_side(lambda: self._wgrad(dg, M, a.ln2[i], D, M, D, a.Tp, gv(self.lname(i, "mlp.fc1.weight")), D))
                 release("dg", li)
                 ops.gemm(dg, mv[ln("mlp.fc1.weight"):], a.dyln, T, D, M, a_layout=K_CONTIG, b_layout=MN_CONTIG, lda=M,
                          ldb=D, ldc=D, epilogue=EPI_BF16)
-                wb ^= 1
+                wb = (wb + 1) % nd
                 acquire("dhb", wb)
-                dhb = a.dhb[wb]
+                dhb = dhbs[wb]
                 bias.ln_bwd(a.dyln, D, a.hm[i], D, a.mu2[i], a.rs2[i], f[ln("norm2.weight"):], a.dh, D, T,
                             gv(self.lname(i, "norm2.weight")), gv(self.lname(i, "attn.out.bias")),
                             dres=a.dh, lddres=D, dx_bf16=dhb, lddxb=D, dx_dropout=dd(1 + 3 * i))
                 # ---- attention: hm = h + out(attn(ln1(h))) ----
                 out_spec = (a.o[i], D, dhb, D, D, D, a.Tp, gv(self.lname(i, "attn.out.weight")), D, 1, 0, 0)
-                if group:  # launched with the q|k|v weight gradient below (dhb stays intact until then)
+                if defer:
+                    pending.append(out_spec)
+                elif group:  # launched with the q|k|v weight gradient below (dhb stays intact until then)
                     out_wb = wb
                 else:
                     on_side(lambda: self._wgrad(*out_spec[:9]))
                     release("dhb", wb)
                 ops.gemm(dhb, mv[ln("attn.out.weight"):], a.dO, T, D, D, a_layout=K_CONTIG, b_layout=K_CONTIG, lda=D,
                          ldb=D, ldc=D, epilogue=EPI_BF16)
-            dqkv = a.dqkv[li]
+            dqkv = dqkvs[li]
             acquire("dqkv", li)
             qpart = bias.buf("qkv", a.qkv_bparts)
             ops.attention_bwd(a.qkv[i], a.o[i], a.dO, a.lse[i], dqkv, b, N, H, hd, scale, bias_partial=qpart,
@@ -777,7 +870,12 @@ class ViTEngine:
             qb = ln("attn.query.bias")
             bias.reduce(qpart, b * a.attn_bias_rows, 3 * D, 3 * D, (g[qb:], g[qb + zs:], g[qb + 2 * zs:]), seg=D)
             qkv_spec = (a.ln1[i], D, dqkv, 3 * D, D, D, a.Tp, g[qo:], D, 3, D, zs)
-            if out_wb is not None:
+            if defer:
+                pending.append(qkv_spec)
+                held += 1
+                if held == defer and i > 0:  # (layer 0's launch also takes the patch embedding's gradient)
+                    flush_wgrad()
+            elif out_wb is not None:
                 # the out-projection (9 tiles at B/16) and q|k|v (27) weight gradients as one grid: one wave of
                 # 252 workgroups at split 7 instead of 252 short ones (split 28) and 243 (split 9)
                 on_side(lambda: self._wgrad_group([out_spec, qkv_spec]))
@@ -789,17 +887,21 @@ class ViTEngine:
                 release("dqkv", li)
             ops.gemm(dqkv, self.wqkv[i], a.dyln, T, D, 3 * D, a_layout=K_CONTIG, b_layout=K_CONTIG, lda=3 * D,
                      ldb=3 * D, ldc=D, epilogue=EPI_BF16)
-            wb ^= 1
+            wb = (wb + 1) % nd
             acquire("dhb", wb)
             bias.ln_bwd(a.dyln, D, a.h[i], D, a.mu1[i], a.rs1[i], f[ln("norm1.weight"):], a.dh, D, T,
                         gv(self.lname(i, "norm1.weight")), gv(self.lname(i - 1, "mlp.fc2.bias")) if i > 0 else None,
-                        dres=a.dh, lddres=D, dx_bf16=a.dhb[wb], lddxb=D,
+                        dres=a.dh, lddres=D, dx_bf16=dhbs[wb], lddxb=D,
                         dx_dropout=dd(3 + 3 * (i - 1)) if i > 0 else dd(0))
             fire(self.layout.buckets[L - i])
         # ---- embedding: conv weight grad (wgrad over patches), bias / pos / cls ----
-        dhb = a.dhb[wb]
-        on_side(lambda: self._wgrad(dhb, D, a.patches, a.kpad, D, cfg.patch_k, a.Tp, gv("embedding.weight"),
-                                    cfg.patch_k))
+        dhb = dhbs[wb]
+        if defer and cfg.patch_k >= 256:
+            pending.append((dhb, D, a.patches, a.kpad, D, cfg.patch_k, a.Tp, gv("embedding.weight"), cfg.patch_k, 1, 0, 0))
+        else:
+            on_side(lambda: self._wgrad(dhb, D, a.patches, a.kpad, D, cfg.patch_k, a.Tp, gv("embedding.weight"),
+                                        cfg.patch_k))
+        flush_wgrad()  # after the last data gradient; the bias and column reductions follow
         ops.embed_grad(a.dh, b, N, D, gv("transformer.pos_embedding.pos_embedding"), gv("cls_token"),
                        gv("embedding.bias"), dropout=dd(0))
         fire(self.layout.buckets[-1])

@@ -613,6 +613,38 @@ def gemm_splitk_group(members):
     check(lib().vit_gemm_splitk_group(arr, len(members), _stream()), "vit_gemm_splitk_group")
 
 
+GEMM_TABLE_MAX = 128  # VIT_GEMM_TABLE_MAX
+
+
+class GemmGroupTable:
+    """A prepared group of split-K weight-gradient GEMMs (vit_gemm_group_prepare): any number of members up to
+    GEMM_TABLE_MAX in ONE launch, their descriptors in a device table that is uploaded once and launched many times.
+    members: [(A, B, C, M, N, K, kwargs, direct)], kwargs as for gemm_splitk_group; a direct member (split_k 1)
+    writes C[z*c_bs + m*ldc + n] itself, the others their packed slabs. Preparing synchronises the current stream."""
+
+    def __init__(self, members):
+        n = len(members)
+        if not 1 <= n <= GEMM_TABLE_MAX:
+            raise ValueError(f"GemmGroupTable: 1 to {GEMM_TABLE_MAX} members")
+        arr = (GemmArgs * n)()
+        direct = (ctypes.c_int32 * n)()
+        for i, (A, B, C, M, N, K, kw, d) in enumerate(members):
+            _chk(A, BF16, "A")
+            _chk(B, BF16, "B")
+            _chk(C, F32, "C")
+            arr[i] = _gemm_args(A, B, C, M, N, K, **kw)
+            direct[i] = int(bool(d))
+        nbytes = int(lib().vit_gemm_group_table_bytes(n))
+        self.table = torch.empty(nbytes, device=members[0][0].device, dtype=torch.uint8)
+        total = ctypes.c_int32(0)
+        check(lib().vit_gemm_group_prepare(arr, direct, n, _p(self.table), nbytes, ctypes.byref(total), _stream()),
+              "vit_gemm_group_prepare")
+        self.n, self.total = n, int(total.value)
+
+    def launch(self):
+        check(lib().vit_gemm_group_launch(_p(self.table), self.n, self.total, _stream()), "vit_gemm_group_launch")
+
+
 def splitk_factor(M, N, K, batch=1, cus=256):
     """split-K factor of a weight-gradient GEMM (K = tokens) on `cus` compute units: the split with the
     least modelled time, ceil(tiles*s / slots) waves of 1/s of a tile's k-range each plus the f32 slab
