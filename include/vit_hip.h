@@ -355,8 +355,13 @@ int vit_gemm_f32(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, i
 
 /* Cross entropy (mean over the global batch), CrossEntropyLoss src/train.py:151,22, plus
  * accuracy counts (src/utils.py:28-41). dlogits = (softmax - onehot) * grad_scale.
- * row_stats[b] = {loss_b, top1_hit, top5_hit}. A label outside [0, C) is not read through: that row's
- * loss and dlogits are NaN. */
+ * row_stats[b] = {loss_b, top1_hit, top5_hit}; dlogits or row_stats may be NULL (not written).
+ * Hits: with above = the number of classes c != label whose logit is greater than the label's or is NaN,
+ * top1_hit = above < 1 and top5_hit = above < 5 (0.0 / 1.0). A NaN logit ranks above every number, as in
+ * torch.topk, so a row of all-NaN logits (a diverged run) is a miss; a row whose only NaN is the label's own
+ * logit is a hit, as in torch. Ties count for the label: a class equal to the label's logit is not above it
+ * (torch's choice among equal logits is unspecified). A row with a NaN logit has a NaN loss and NaN dlogits.
+ * A label outside [0, C) is not read through: that row's loss and dlogits are NaN and it is a miss. */
 int vit_cross_entropy(const float* logits, const int64_t* labels, int64_t B, int64_t C,
                       float* dlogits, float grad_scale, float* row_stats, vit_stream_t stream);
 
@@ -399,7 +404,8 @@ int vit_pack_cols_batched(const float* in, int64_t in_batch_stride, int64_t zstr
  * LinearGeneral q/k/v/out src/model.py:73-76). */
 int vit_transpose_f32_bf16(const float* in, int64_t rows, int64_t cols, int64_t ldi, void* out, int64_t ldo,
                            int64_t batch, int64_t in_batch_stride, int64_t out_batch_stride, vit_stream_t stream);
-/* y = a*x + b*y (f32), used for gradient scaling / accumulation. */
+/* y = a*x + b*y (f32), used for gradient scaling / accumulation. b == 0 means y is not read: y = a*x even where
+ * y held NaN or Inf (an uninitialised buffer), BLAS's beta == 0 rule. x == y (in place) is allowed. */
 int vit_axpby(const float* x, float* y, int64_t n, float a, float b, vit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------

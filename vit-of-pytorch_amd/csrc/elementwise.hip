@@ -355,10 +355,13 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   __syncthreads();
   const float xy = ok ? x[y] : __builtin_nanf("");
+  // rank of the label: the other classes above it. A NaN logit ranks above every number (torch.topk's order, which
+  // the reference's accuracy() uses), so a diverged row is a miss, not a hit; ties count for the label
   float s = 0.f, gt = 0.f;
   for (int c = threadIdx.x; c < C; c += 256) {
-    s += __expf(x[c] - mx);
-    gt += x[c] > xy ? 1.f : 0.f;
+    const float xc = x[c];
+    s += __expf(xc - mx);
+    gt += c != y && (xc > xy || __builtin_isnan(xc)) ? 1.f : 0.f;
   }
   s = wave_sum(s);
   gt = wave_sum(gt);
@@ -378,8 +381,8 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
   }
   if (threadIdx.x == 0 && row_stats) {
     row_stats[b * 3 + 0] = lse - xy;
-    row_stats[b * 3 + 1] = gt < 1.f ? 1.f : 0.f;
-    row_stats[b * 3 + 2] = gt < 5.f ? 1.f : 0.f;
+    row_stats[b * 3 + 1] = ok && gt < 1.f ? 1.f : 0.f;
+    row_stats[b * 3 + 2] = ok && gt < 5.f ? 1.f : 0.f;
   }
 }
 
@@ -446,7 +449,8 @@ __global__ void cast_pad_kernel(const float* __restrict__ in, long rows, long co
     out[i] = c < cols ? f2bf(in[r * cols + c]) : (bf16_t)0;
   }
 }
-__global__ void axpby_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float a, float b) {
+// (x may be y: no __restrict__)
+__global__ void axpby_kernel(const float* x, float* y, long n, float a, float b) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     y[i] = a * x[i] + (b == 0.f ? 0.f : b * y[i]);
 }

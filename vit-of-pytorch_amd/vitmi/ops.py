@@ -476,16 +476,16 @@ def router_head_bwd(soft, ysoft, dsoft, dhard, dind, dent, N, reserve, training,
     return dl
 
 
-def cls_mse(x, ldx, t, ldt, B, D):
+def cls_mse(x, ldx, t, ldt, B, D, return_part=False):
     """(loss [], e [B][D]) with e = x rows - t rows (row strides ldx / ldt floats) and loss = mean(e^2)
-    (vit_cls_mse)"""
+    (vit_cls_mse); return_part: also the per-row sums of e^2, part [B]"""
     _chk(x, F32, "x")
     _chk(t, F32, "t")
     e = torch.empty(B, D, device=x.device, dtype=F32)
     part = torch.empty(B, device=x.device, dtype=F32)
     loss = torch.empty((), device=x.device, dtype=F32)
     check(lib().vit_cls_mse(_p(x), ldx, _p(t), ldt, B, D, _p(e), _p(part), _p(loss), _stream()), "vit_cls_mse")
-    return loss, e
+    return (loss, e, part) if return_part else (loss, e)
 
 
 def cls_mse_bwd(dx, lddx, e, g):
