@@ -191,6 +191,10 @@ int vit_splitk_reduce_group(const vit_splitk_job* jobs, int32_t njobs, vit_strea
  *      reduce later (vit_colsum3 over [nblk][3*D], e.g. on another stream).
  *      dx_dropout (optional): the bf16 copy and dx_colsum carry dx_out * mult (the gradient of the
  *      dropout-ed branch that fed the residual stream); dx itself stays unmasked.
+ * D is a multiple of 4, at most 2048. Rows are accessed in 16-B (f32) / 8-B (bf16) vectors: every base pointer must
+ * be 16-B aligned (8-B for bf16; not checked), and every row stride a call uses must be a multiple of 4 elements:
+ * ldx and ldy forward; lddy, ldx, lddx, lddres when dres is given and lddxb when dx_bf16 is given backward. A D or
+ * a stride that is not returns VIT_ERR_INVALID_ARG before any launch.
  * ---------------------------------------------------------------------------------------- */
 int vit_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta,
                       void* y, int64_t ldy, int32_t y_f32, float* mean, float* rstd,

@@ -1,6 +1,7 @@
 """Float64 references, exact operand builders and per-element gates for the step's glue kernels
 (csrc/elementwise.hip, csrc/optim.hip): column sums, embedding gradients, the f32 GEMM, casts / packs / transposes,
-GELU, cross entropy, the cls MSE, SGD and AdamW.
+GELU, cross entropy, the cls MSE, SGD and AdamW, and the Res-ViT router kernels (segment sums, the gated data gradient,
+the router head, the routing masks).
 
 A helper module, not a test file (the tests import it as `glue_ref`); plain torch, so it runs on CPU and GPU
 tensors alike.
@@ -434,3 +435,312 @@ def adamw_layout(lengths=ADAMW_LENGTHS, chunk=8192, inactive=2):
             chunks.append([s, at + c0, min(chunk, n - c0)])
         at += (n + 63) // 64 * 64
     return starts, at, torch.tensor(chunks, dtype=torch.int64), [s != inactive for s in range(len(lengths))]
+
+
+# ---- Res-ViT router kernels --------------------------------------------------------------------------------------------
+def segment_colsum(x, segs, seg_rows, seg_stride, row0, scale):
+    """float64 [segs, cols] of vit_segment_colsum: scale times the sum of rows [s seg_stride + row0, + seg_rows) of x.
+    On integer operands (assert_exact_sum) and a power-of-two scale every partial sum and the product are exact."""
+    out = torch.zeros(segs, x.shape[1], dtype=torch.float64, device=x.device)
+    for s in range(segs):
+        r0 = s * seg_stride + row0
+        out[s] = x[r0:r0 + seg_rows].double().sum(0) * scale
+    return out
+
+
+def segment_colsum_emulate(x, segs, seg_rows, seg_stride, row0, scale, unroll_bound=12):
+    """the kernel's order in f32: four row lanes, lane l adds rows l, l + 4, ... (four at a time while
+    r + 12 < seg_rows, then one at a time), then lanes 0..3 in turn, then the scale. unroll_bound: the planted
+    fault (r + 8 < seg_rows reads three rows past the segment)"""
+    out = torch.zeros(segs, x.shape[1])
+    for s in range(segs):
+        base = s * seg_stride + row0
+        lanes = []
+        for l in range(4):
+            acc, r = torch.zeros(x.shape[1]), l
+            while r + unroll_bound < seg_rows:
+                for k in (0, 4, 8, 12):
+                    acc = acc + x[base + r + k].float()
+                r += 16
+            while r < seg_rows:
+                acc = acc + x[base + r].float()
+                r += 4
+            lanes.append(acc)
+        out[s] = (((lanes[0] + lanes[1]) + lanes[2]) + lanes[3]) * torch.tensor(scale, dtype=torch.float32)
+    return out
+
+
+RDG_RB = 32     # rows per column-partial block of vit_router_dx_gate
+
+
+def router_dx_gate(dx, g, g_scale, gp, T, N, reserve, rows_pad, cols_pad):
+    """vit_router_dx_gate from CPU f32 operands dx [T, cols], g [ceil(T / N), cols], gp bf16 [T, cols]:
+    (out bf16 [rows_pad, cols_pad], col_partial float64 [ceil(rows_pad / 32), cols]).
+    out = bf16((dx + s g[t // N]) gp), s = g_scale where t % N >= reserve, else the term is absent; the product s g,
+    the sum and the product with gp each rounded to f32 (torch's CPU f32 operators, which never fuse), then one
+    round-to-nearest-even to bf16: compared as bit patterns. Zeros in the padding. col_partial: per 32-row block, the
+    column sums of the rounded values; exact in f32 when they are small integers or halves."""
+    cols = dx.shape[1]
+    t = torch.arange(T)
+    term = torch.tensor(g_scale, dtype=torch.float32) * g.float()[t // N]
+    term = torch.where(((t % N) >= reserve)[:, None], term, torch.zeros_like(term))
+    val = ((dx.float() + term) * gp.float()).bfloat16()
+    out = torch.zeros(rows_pad, cols_pad, dtype=torch.bfloat16)
+    out[:T, :cols] = val
+    nblk = -(-rows_pad // RDG_RB)
+    full = torch.zeros(nblk * RDG_RB, cols, dtype=torch.float64)
+    full[:T] = val.double()
+    return out, full.reshape(nblk, RDG_RB, cols).sum(1)
+
+
+def router_select(idx, sets, nkeys):
+    """vit_router_select: (active bool [npos, T], sel bool [nkeys, T], any bool [nkeys]); active[j] = isin(trunc(idx),
+    sets[j]) with the truncation toward zero of torch's .long() (so -0.5 -> 0); NaN and values whose truncation is
+    outside [0, 32) are in no set (their conversion is not performed: it is undefined for NaN and 1e9 alike);
+    sel[k] = idx == k"""
+    T = idx.numel()
+    ok = (idx > -1) & (idx < 32)
+    lv = torch.where(ok, idx, torch.zeros_like(idx)).long()
+    active = torch.zeros(len(sets), T, dtype=torch.bool)
+    for j, st in enumerate(sets):
+        active[j] = ok & torch.isin(lv, torch.tensor(sorted(st), dtype=torch.int64))
+    sel = torch.stack([idx == float(k) for k in range(nkeys)]) if nkeys else torch.zeros(0, T, dtype=torch.bool)
+    return active, sel, sel.any(1)
+
+
+ROUTER_SELECT_VALUES = (-0.5, -1.0, 3.5, 31.0, 32.0, 1e9, NAN, 0.0, -0.0, 5.0, 7.0)
+
+
+def router_select_case(T, gen):
+    """pattern indices f32 [T]: integers 0..31 with the edge values strewn in; key 13 appears in the last token only"""
+    idx = torch.randint(0, 32, (T,), generator=gen).float()
+    idx[idx == 13.0] = 12.0
+    edge = torch.tensor(ROUTER_SELECT_VALUES)
+    n = min(T - 1, edge.numel())
+    if n > 0:
+        at = torch.randperm(T - 1, generator=gen)[:n]
+        idx[at] = edge[:n]
+    idx[T - 1] = 13.0
+    return idx
+
+
+# ---- Res-ViT router head ---------------------------------------------------------------------------------------------
+RH_THREADS = 256
+RH_SLACK = 1.0 + 2.0 ** -9      # second-order products of the counted terms
+RH_C = 1e-8                     # the entropy's p + 1e-8 (as f32)
+
+
+def _softmax2(a, b, darg):
+    """float64 two-element softmax of the arguments a, b and its gate. The kernel's softmax2 is max, two expf, one
+    addition, two divisions. With d = |a - b|: the larger argument gives expf(0) = 1 exactly; the other's argument
+    a - max is rounded (u d absolute, so u d relative on the exponential) and expf is good to 1 ulp (2 u):
+    eps_e = (d + 2) u. The sum 1 + e adds u, each division 1 ulp (2 u): rel(p) <= eps_e + (u + eps_e) + 2 u
+    = (2 d + 7) u. darg: the absolute error of a - b already in the arguments (noise added in f32); it moves either
+    probability by at most p darg (dp/dd = p0 p1)."""
+    m = torch.maximum(a, b)
+    e0, e1 = torch.exp(a - m), torch.exp(b - m)
+    p0, p1 = e0 / (e0 + e1), e1 / (e0 + e1)
+    rel = RH_SLACK * ((2 * (a - b).abs() + 7) * UF + darg)
+    return p0, p1, rel * p0, rel * p1
+
+
+def router_head_fwd(logits, noise, noise_mode, yhard, N, reserve, training, norm):
+    """float64 reference and gates of vit_router_head_fwd (logits [T, bs, 2] CPU f32). Returns an object with
+    soft / b_soft; ysoft / b_ysoft (training); hard (the expected values: the one-hot, the caller's y_hard, (0, 1) on
+    reserved tokens) with b_hard (0 in evaluation: equal; 2 u in training, the two roundings of (y_hard - y) + y) and
+    `decided` [T, bs], false where the float64 margin |y1 - y0| is within the softmax gates (the one-hot may
+    legitimately differ there; an exact tie of equal arguments is decided: index 0); indices [T] with b_idx and
+    idx_decided [T]; ent with b_ent.
+    Entropy: each term t = p log(p + 1e-8) carries |t| (rel(p) + 3 u) + p (rel(p) + u) (the probability, the
+    addition, logf's 1 ulp, the product); the sum of the two terms, the bs positions, the 8-level tree of a block,
+    the strided sum over ceil(blocks / 256) partials, another 8-level tree and the division by norm are
+    n = bs + 19 + ceil(blocks / 256) roundings of a sum of same-signed terms: n u sum|t|."""
+    r = CE()
+    T, bs, _ = logits.shape
+    x = logits.double()
+    zero = torch.zeros(T, bs, dtype=torch.float64)
+    r.soft0, r.soft1, r.b_soft0, r.b_soft1 = _softmax2(x[..., 0], x[..., 1], zero)
+    r.soft = torch.stack([r.soft0, r.soft1], -1)
+    r.b_soft = torch.stack([r.b_soft0, r.b_soft1], -1)
+    res = ((torch.arange(T) % N) < reserve)[:, None].expand(T, bs)
+    c = f32(RH_C)
+    t = r.soft * torch.log(r.soft + c)
+    relp = r.b_soft / r.soft.clamp_min(1e-300)
+    dt = t.abs() * (relp + 3 * UF) + r.soft * (relp + UF)
+    live = (~res)[..., None]
+    nb = -(-T // RH_THREADS)
+    n = bs + 19 + -(-nb // RH_THREADS)
+    norm = f32(norm)
+    r.ent = -(t * live).sum() / norm
+    r.b_ent = RH_SLACK * ((dt * live).sum() + n * UF * (t.abs() * live).sum()) / norm
+    if training:
+        g = torch.zeros_like(x)
+        darg = zero
+        if noise_mode == 1:
+            g = noise.double()
+        elif noise_mode == 2:
+            g = -torch.log(noise.double())
+        a = x + g
+        if noise_mode:      # the f32 sum's rounding, and logf's 1 ulp on the noise
+            darg = (UF * a.abs() + (2 * UF * g.abs() if noise_mode == 2 else 0)).sum(-1)
+        y0, y1, b0, b1 = _softmax2(a[..., 0], a[..., 1], darg)
+        r.ysoft, r.b_ysoft = torch.stack([y0, y1], -1), torch.stack([b0, b1], -1)
+        q0, q1, m0, m1 = y0, y1, b0, b1
+        if noise_mode == 1:     # the kernel's own f32 sums logits + noise (one addition: torch's is the same one)
+            a32 = logits + noise
+            equal_args = a32[..., 0] == a32[..., 1]
+        else:
+            equal_args = (logits[..., 0] == logits[..., 1]) & (
+                True if not noise_mode else (noise[..., 0] == noise[..., 1]))
+    else:
+        q0, q1, m0, m1 = r.soft0, r.soft1, r.b_soft0, r.b_soft1
+        equal_args = logits[..., 0] == logits[..., 1]
+    if yhard is not None:
+        hard = yhard.double().clone()
+        r.decided = torch.ones(T, bs, dtype=torch.bool)
+    else:
+        h1 = (q1 > q0).double()
+        hard = torch.stack([1 - h1, h1], -1)
+        r.decided = ((q1 - q0).abs() > m0 + m1) | equal_args
+        hard = torch.where(equal_args[..., None], torch.tensor([1.0, 0.0], dtype=torch.float64), hard)
+    hard = torch.where(res[..., None], torch.tensor([0.0, 1.0], dtype=torch.float64), hard)
+    r.decided = r.decided | res
+    r.hard = hard
+    straight = training & ~res      # (y_hard - y) + y: two roundings of values of size at most 1 + |y_hard|
+    r.b_hard = torch.where(straight[..., None], 2 * UF * RH_SLACK * hard.abs().clamp_min(1.0), torch.zeros_like(hard))
+    w = 2.0 ** torch.arange(bs - 1, -1, -1, dtype=torch.float64)
+    r.indices = (hard[..., 1] * w).sum(1)
+    # the fma chain: bs roundings of a partial index below 2^bs max|hard|, plus the hard values' own error
+    r.b_idx = (r.b_hard[..., 1] * w).sum(1) + torch.where(
+        straight.any(1), RH_SLACK * bs * UF * (hard[..., 1].abs() * w).sum(1), torch.zeros(T, dtype=torch.float64))
+    r.idx_decided = r.decided.all(1)
+    return r
+
+
+def router_head_fwd_emulate(logits, noise, noise_mode, yhard, N, reserve, training, norm):
+    """the kernel's formulas in f32 torch, unfused: (soft, ysoft or None, hard, indices, entropy)"""
+    def sm(a, b):
+        m = torch.maximum(a, b)
+        e0, e1 = torch.exp(a - m), torch.exp(b - m)
+        s = e0 + e1
+        return e0 / s, e1 / s
+    T, bs, _ = logits.shape
+    t32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    l0, l1 = logits[..., 0], logits[..., 1]
+    p0, p1 = sm(l0, l1)
+    res = ((torch.arange(T) % N) < reserve)[:, None].expand(T, bs)
+    term = p0 * torch.log(p0 + t32(RH_C)) + p1 * torch.log(p1 + t32(RH_C))
+    ent = -(torch.where(res, torch.zeros_like(term), term).sum()) / t32(norm)
+    ysoft = None
+    if training:
+        g0 = g1 = torch.zeros_like(l0)
+        if noise_mode == 1:
+            g0, g1 = noise[..., 0], noise[..., 1]
+        elif noise_mode == 2:
+            g0, g1 = -torch.log(noise[..., 0]), -torch.log(noise[..., 1])
+        y0, y1 = sm(l0 + g0, l1 + g1)
+        ysoft = torch.stack([y0, y1], -1)
+        if yhard is not None:
+            yh0, yh1 = yhard[..., 0], yhard[..., 1]
+        else:
+            yh1 = (y1 > y0).float()
+            yh0 = 1 - yh1
+        h0, h1 = (yh0 - y0) + y0, (yh1 - y1) + y1
+    elif yhard is not None:
+        h0, h1 = yhard[..., 0], yhard[..., 1]
+    else:
+        h1 = (p1 > p0).float()
+        h0 = 1 - h1
+    h0 = torch.where(res, torch.zeros_like(h0), h0)
+    h1 = torch.where(res, torch.ones_like(h1), h1)
+    idx = torch.zeros(T)
+    for i in range(bs):
+        idx = h1[:, i] * t32(float(1 << (bs - 1 - i))) + idx
+    return torch.stack([p0, p1], -1), ysoft, torch.stack([h0, h1], -1), idx, ent
+
+
+def router_head_bwd(soft, ysoft, dsoft, dhard, dind, dent, N, reserve, training, norm):
+    """float64 dlogits [T, bs, 2] of vit_router_head_bwd from the f32 soft / ysoft it is given, and its gate. With
+    c = 1e-8, L = log(p + c), q = p / (p + c), ge = -dent / norm on non-reserved tokens (else the term is absent):
+        A = L + q                   e_A  = u + 2 u |L| + 3 u q + u |A|   (p + c; logf's 1 ulp; the division; the sum)
+        d = dsoft + ge A            e_d  = |ge| e_A + 3 u |ge A| + u |d|  (ge's division 2 u, the product, the sum)
+        sd = d0 p0 + d1 p1          e_sd = sum p e_d + 2 u sum |d p|      (the two products, the sum)
+        o = p (d - sd)              e_o  = p (e_d + e_sd + u |d - sd|) + u |o|
+    and in training on non-reserved tokens with dhard or dind, h = dhard, h1 += dind 2^(bs-1-i) (e_h1 = u |h1|),
+    sy = h0 y0 + h1 y1, o += y (h - sy) with the same three-product count, and u |o| for the final sum."""
+    T, bs, _ = soft.shape
+    p = soft.double()
+    res = ((torch.arange(T) % N) < reserve)[:, None, None]
+    norm = f32(norm)
+    c = f32(RH_C)
+    d = torch.zeros_like(p) if dsoft is None else dsoft.double()
+    e_d = torch.zeros_like(p)
+    if dent is not None:
+        ge = torch.where(res, torch.zeros(1, dtype=torch.float64), -dent.double() / norm)
+        L, q = torch.log(p + c), p / (p + c)
+        A = L + q
+        e_A = UF * (1 + 2 * L.abs() + 3 * q + A.abs())
+        d = d + ge * A
+        e_d = torch.where(ge != 0, ge.abs() * e_A + 3 * UF * (ge * A).abs() + UF * d.abs(), e_d)
+    sd = (d * p).sum(-1, keepdim=True)
+    e_sd = (p * e_d).sum(-1, keepdim=True) + 2 * UF * (d * p).abs().sum(-1, keepdim=True)
+    o = p * (d - sd)
+    e_o = p * (e_d + e_sd + UF * (d - sd).abs()) + UF * o.abs()
+    if training and ysoft is not None and (dhard is not None or dind is not None):
+        y = ysoft.double()
+        h = torch.zeros_like(p) if dhard is None else dhard.double().clone()
+        e_h = torch.zeros_like(p)
+        if dind is not None:
+            w = 2.0 ** torch.arange(bs - 1, -1, -1, dtype=torch.float64)
+            h[..., 1] = h[..., 1] + dind.double()[:, None] * w[None, :]
+            e_h[..., 1] = UF * h[..., 1].abs()
+        sy = (h * y).sum(-1, keepdim=True)
+        e_sy = (y * e_h).sum(-1, keepdim=True) + 2 * UF * (h * y).abs().sum(-1, keepdim=True)
+        t2 = y * (h - sy)
+        e_t2 = y * (e_h + e_sy + UF * (h - sy).abs()) + UF * t2.abs()
+        o = torch.where(res, o, o + t2)
+        e_o = torch.where(res, e_o, e_o + e_t2 + UF * o.abs())
+    return o, RH_SLACK * e_o
+
+
+def router_head_bwd_emulate(soft, ysoft, dsoft, dhard, dind, dent, N, reserve, training, norm, reserved_take_hard=False,
+                            ent_sign=-1.0):
+    """the kernel's formulas in f32 torch, unfused. Planted faults: reserved tokens take the hard gradient; the
+    entropy gradient with the wrong sign (ent_sign 1)"""
+    T, bs, _ = soft.shape
+    t32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    res = ((torch.arange(T) % N) < reserve)[:, None, None]
+    p = soft
+    d = torch.zeros_like(p) if dsoft is None else dsoft.clone()
+    if dent is not None:
+        ge = torch.where(res, torch.zeros(1), ent_sign * dent / t32(norm))
+        A = torch.log(p + t32(RH_C)) + p / (p + t32(RH_C))
+        d = torch.where(ge != 0, d + ge * A, d)
+    sd = d[..., :1] * p[..., :1] + d[..., 1:] * p[..., 1:]
+    o = p * (d - sd)
+    if training and ysoft is not None and (dhard is not None or dind is not None):
+        h = torch.zeros_like(p) if dhard is None else dhard.clone()
+        if dind is not None:
+            w = torch.tensor([float(1 << (bs - 1 - i)) for i in range(bs)])
+            h[..., 1] = h[..., 1] + dind[:, None] * w[None, :]
+        sy = h[..., :1] * ysoft[..., :1] + h[..., 1:] * ysoft[..., 1:]
+        o2 = o + ysoft * (h - sy)
+        o = o2 if reserved_take_hard else torch.where(res, o, o2)
+    return o
+
+
+def router_head_logits(T, bs, gen, ties=True):
+    """logits: multiples of 1/8 in [-4, 4]; with Gumbel noise in multiples of 1/4 every argument difference is 0 (a
+    tie, decided: index 0) or at least 1/8 (|y1 - y0| >= tanh(1/16) = 0.06, far above the softmax gate), so the
+    reference alone never has to skip a decision. ties: a few exact ties planted."""
+    x = torch.randint(-32, 33, (T, bs, 2), generator=gen).float() / 8
+    if ties:
+        x[::7, 0, 1] = x[::7, 0, 0]
+    return x
+
+
+def router_head_noise(T, bs, mode, gen):
+    """mode 1: Gumbel-like noise in multiples of 1/4 in [-2, 2]; mode 2: exponential draws in [2^-20, 1]"""
+    if mode == 1:
+        return torch.randint(-8, 9, (T, bs, 2), generator=gen).float() / 4
+    return torch.rand(T, bs, 2, generator=gen).clamp_min(2.0 ** -20)

@@ -1,7 +1,9 @@
 """The per-element gates of glue_ref.py, proved without a GPU: each float64 reference is the operation torch
 computes, a correctly rounded f32 evaluation of each kernel's formula passes its gate, and the small planted faults
 that a whole-tensor norm lets through (one wrong tail element, a dropped last chunk, a row shifted by one, a segment
-written to the wrong output, a touched guard column, a NaN-logit row counted as a hit) are rejected."""
+written to the wrong output, a touched guard column, a NaN-logit row counted as a hit; for the router kernels an unrolled
+loop entered one group early, a truncating pack, reserve off by one, a late image index, ties taking index 1, the entropy
+over reserved tokens or with the wrong sign, reserved tokens taking the hard gradient) are rejected."""
 import math
 
 import pytest
@@ -408,3 +410,160 @@ def test_adamw_layout_by_hand():
     assert chunks.shape == (9, 3) and int(chunks[:, 2].max()) == 8192
     for s, n in enumerate(G.ADAMW_LENGTHS):
         assert int(chunks[chunks[:, 0] == s][:, 2].sum()) == n
+
+
+# ---- Res-ViT router kernels --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seg_rows", [0, 1, 3, 4, 5, 12, 13, 15, 16, 17, 29, 33])
+def test_segment_colsum_gate_and_unroll_bound(seg_rows):
+    G.assert_exact_sum(seg_rows + 12, 8)
+    segs, row0, scale, cols = 3, 2, 0.25, 5
+    stride = row0 + seg_rows + 3
+    x = G.ints((segs * stride + 16, cols), _gen(seg_rows), 1, 8)             # (positive: a row read too many shows)
+    want = G.segment_colsum(x, segs, seg_rows, stride, row0, scale).float()
+    assert G.first_diff(G.segment_colsum_emulate(x, segs, seg_rows, stride, row0, scale), want) is None
+    assert G.first_diff(G.segment_colsum_emulate(x.bfloat16(), segs, seg_rows, stride, row0, scale), want) is None
+    # the unrolled loop entered at r + 8 < seg_rows reads row r + 12 past the segment for some row lane
+    bad = G.segment_colsum_emulate(x, segs, seg_rows, stride, row0, scale, unroll_bound=8)
+    reads_past = any(l + 8 < seg_rows <= l + 12 for l in range(4)) or any(
+        l + 16 + 8 < seg_rows <= l + 16 + 12 for l in range(4))
+    assert (G.first_diff(bad, want) is not None) == reads_past
+    if seg_rows:
+        assert G.first_diff(G.segment_colsum_emulate(x, segs, seg_rows, stride, row0 + 1, scale), want) is not None
+
+
+@pytest.mark.parametrize("T,N,reserve", [(9, 3, 1), (33, 5, 0), (65, 50, 50), (7, 1, 1)])
+def test_router_dx_gate_reference(T, N, reserve):
+    cols, rows_pad, cols_pad = 6, T + 35, 8
+    imgs = -(-T // N)
+    g0 = _gen(T)
+    dx, g = torch.randn(T, cols, generator=g0), torch.randn(imgs, cols, generator=g0)
+    gp = torch.randn(T, cols, generator=g0).bfloat16()
+    out, part = G.router_dx_gate(dx, g, 0.3, gp, T, N, reserve, rows_pad, cols_pad)
+    assert out.shape == (rows_pad, cols_pad) and part.shape == (-(-rows_pad // 32), cols)
+    assert float(out[T:].float().abs().max()) == 0.0 and float(out[:, cols:].float().abs().max()) == 0.0
+    # element by element: three f32 roundings, then the independent integer round-to-nearest-even
+    s = torch.tensor(0.3, dtype=torch.float32)
+    loop = torch.empty(T, cols)
+    for t in range(T):
+        v = dx[t] + s * g[t // N] if t % N >= reserve else dx[t]
+        loop[t] = v * gp[t].float()
+    bits = out[:T, :cols].contiguous().view(torch.int16).to(torch.int64) & 0xffff
+    assert torch.equal(bits, G.bf16_rne_bits(loop).reshape(T, cols))
+    # planted: one rounding of the exact value (a fused evaluation), a truncating pack, reserve off by one, the image
+    # index advanced one row late
+    t = torch.arange(T)
+    live = ((t % N) >= reserve)[:, None]
+    trunc = (loop.view(torch.int32) >> 16).to(torch.int64) & 0xffff
+    assert not torch.equal(trunc, bits)
+    if N > 1 or reserve == 0:
+        other = G.router_dx_gate(dx, g, 0.3, gp, T, N, (reserve + 1) % (N + 1), rows_pad, cols_pad)[0]
+        assert G.first_diff(other, out, bits=True) is not None
+    if imgs > 1 and reserve == 0:       # (with N = 1 every row names its own row of g)
+        late = G.router_dx_gate(dx, g[((t - 1).clamp(min=0)) // N], 0.3, gp, T, 1, 0, rows_pad, cols_pad)[0]
+        assert G.first_diff(late, out, bits=True) is not None
+    # integer operands: the partials are exact, and a block's sum that skips its last data row is not
+    G.assert_exact_sum(32, 96)
+    dxi, gi = G.ints((T, cols), g0), G.ints((imgs, cols), g0)
+    gpi = G.ints((T, cols), g0, 1, 4).bfloat16()
+    outi, parti = G.router_dx_gate(dxi, gi, 0.5, gpi, T, N, reserve, rows_pad, cols_pad)
+    seq = torch.zeros(parti.shape[0], cols)
+    for r in range(T):
+        seq[r // 32] = seq[r // 32] + outi[r, :cols].float()
+    assert G.first_diff(seq, parti.float()) is None
+    assert float(parti[-1].abs().max()) == 0.0                                   # a whole padding block
+    assert torch.equal(outi[:T, :cols].float().double(), ((dxi.double() + torch.where(
+        live, 0.5 * gi.double()[t // N], torch.zeros(T, cols, dtype=torch.float64))) * gpi.double()))
+
+
+def test_router_select_reference():
+    idx = G.router_select_case(4101, _gen(1))
+    sets = [{0, 3, 31}, {1}, set(), set(range(32))]
+    active, sel, anyf = G.router_select(idx, sets, 32)
+    defined = ~idx.isnan() & (idx.abs() < 1e6)          # where torch's .long() is defined
+    for j, st in enumerate(sets):
+        want = torch.isin(idx[defined].long(), torch.tensor(sorted(st), dtype=torch.int64))
+        assert torch.equal(active[j][defined], want)
+        assert not bool(active[j][~defined].any())
+    at = {float(v): int((idx == v).nonzero()[0]) for v in (-0.5, -1.0, 3.5, 31.0, 32.0)}
+    assert bool(active[0][at[-0.5]]) and not bool(active[3][at[-1.0]]) and bool(active[0][at[3.5]])
+    assert bool(active[0][at[31.0]]) and not bool(active[3][at[32.0]])
+    assert not bool(sel[:, idx.isnan()].any()) and not bool(sel[3][at[3.5]])
+    assert bool(anyf[13]) and int(sel[13].sum()) == 1 and bool(sel[13][-1])
+    assert torch.equal(sel[0], idx == 0) and bool(sel[0][(idx == 0) & (torch.signbit(idx))].all())    # -0.0 == 0
+    assert G.router_select(idx, [], 0)[1].shape == (0, 4101)
+
+
+# (T, bs, N, reserve, noise_mode, training, y_hard given)
+HEAD_CASES = [(513, 8, 57, 1, 1, True, False), (257, 2, 3, 0, 2, True, False), (255, 1, 5, 5, 0, True, True),
+              (513, 8, 57, 1, 0, False, False), (256, 2, 4, 1, 0, False, True), (1, 8, 1, 0, 0, True, False)]
+
+
+def _head_inputs(T, bs, mode, yh, seed):
+    g = _gen(seed)
+    x = G.router_head_logits(T, bs, g)
+    noise = G.router_head_noise(T, bs, mode, g) if mode else None
+    yhard = None
+    if yh:
+        h1 = torch.randint(0, 2, (T, bs), generator=g).float()
+        yhard = torch.stack([1 - h1, h1], -1)
+    return x, noise, yhard, g
+
+
+@pytest.mark.parametrize("T,bs,N,reserve,mode,training,yh", HEAD_CASES)
+def test_router_head_gates(T, bs, N, reserve, mode, training, yh):
+    x, noise, yhard, g = _head_inputs(T, bs, mode, yh, T + bs)
+    r = G.router_head_fwd(x, noise, mode, yhard, N, reserve, training, 100.0)
+    soft, ysoft, hard, idx, ent = G.router_head_fwd_emulate(x, noise, mode, yhard, N, reserve, training, 100.0)
+    assert float((r.soft - torch.softmax(x.double(), -1)).abs().max()) < 1e-15
+    assert G.worst(soft, r.soft, r.b_soft)[0] <= 1.0
+    if training:
+        assert G.worst(ysoft, r.ysoft, r.b_ysoft)[0] <= 1.0
+    # the 1 % cap on undecided one-hots holds on the reference alone (and the Gumbel grid leaves none)
+    skipped = float((~r.decided).double().mean())
+    assert skipped <= 0.01 and (mode == 2 or skipped == 0.0)
+    sel = lambda got, ref, m: torch.where(m, got.double(), ref)
+    assert G.worst(sel(hard, r.hard, r.decided[..., None]), r.hard, r.b_hard)[0] <= 1.0
+    assert G.worst(sel(idx, r.indices, r.idx_decided), r.indices, r.b_idx)[0] <= 1.0
+    if not training:
+        assert float(r.b_hard.max()) == 0.0 and float(r.b_idx.max()) == 0.0                  # evaluation: equal
+    assert G.worst(ent.reshape(1), r.ent.reshape(1), r.b_ent.reshape(1))[0] <= 1.0
+    res = (torch.arange(T) % N) < reserve
+    assert torch.equal(r.hard[res], torch.tensor([0.0, 1.0], dtype=torch.float64).expand(int(res.sum()), bs, 2))
+    if not yh:
+        tie = (x[..., 0] == x[..., 1]) & ~res[:, None] if mode == 0 else torch.zeros(T, bs, dtype=torch.bool)
+        assert bool((r.hard[tie][:, 0] == 1.0).all()) and bool(r.decided[tie].all())         # exact ties: index 0
+        if mode == 0 and bool(tie.any()):
+            bad = hard.clone()
+            bad[tie] = torch.tensor([0.0, 1.0])                                               # ties taking index 1
+            assert not G.worst(sel(bad, r.hard, r.decided[..., None]), r.hard, r.b_hard)[0] <= 1.0
+    if reserve and reserve < N:
+        # the entropy summed over the reserved tokens too
+        bad = G.router_head_fwd_emulate(x, noise, mode, yhard, N, 0, training, 100.0)[4]
+        assert G.worst(bad.reshape(1), r.ent.reshape(1), r.b_ent.reshape(1))[0] > 1.0
+    # backward, from the f32 soft / ysoft, with each gradient absent in turn
+    grads = [torch.randn(T, bs, 2, generator=g), torch.randn(T, bs, 2, generator=g), torch.randn(T, generator=g),
+             torch.randn((), generator=g)]
+    for drop in range(5):
+        a = [None if k == drop else t for k, t in enumerate(grads)]
+        ref, bound = G.router_head_bwd(soft, ysoft, *a, N, reserve, training, 100.0)
+        assert G.worst(G.router_head_bwd_emulate(soft, ysoft, *a, N, reserve, training, 100.0), ref, bound)[0] <= 1.0
+        if a[3] is not None and reserve < N:
+            bad = G.router_head_bwd_emulate(soft, ysoft, *a, N, reserve, training, 100.0, ent_sign=1.0)
+            assert G.worst(bad, ref, bound)[0] > 1.0
+        if training and reserve and (a[1] is not None or a[2] is not None):
+            bad = G.router_head_bwd_emulate(soft, ysoft, *a, N, reserve, training, 100.0, reserved_take_hard=True)
+            assert G.worst(bad, ref, bound)[0] > 1.0
+    # the reference is autograd's gradient of the same function
+    if training and not yh and mode != 2:
+        xr = x.double().requires_grad_(True)
+        p = torch.softmax(xr, -1)
+        y = torch.softmax(xr + (noise.double() if mode else 0), -1)
+        live = (~res)[:, None, None].double()
+        entv = -(p * torch.log(p + G.f32(G.RH_C)) * live).sum() / 100.0
+        w = 2.0 ** torch.arange(bs - 1, -1, -1, dtype=torch.float64)
+        hardv = torch.where(res[:, None, None], torch.tensor([0.0, 1.0], dtype=torch.float64), (r.hard - y.detach()) + y)
+        loss = (p * grads[0].double()).sum() + (hardv * grads[1].double()).sum() + \
+            ((hardv[..., 1] * w).sum(1) * grads[2].double()).sum() + entv * grads[3].double()
+        gx, = torch.autograd.grad(loss, xr)
+        ref, _ = G.router_head_bwd(p.detach().float(), y.detach().float(), *grads, N, reserve, training, 100.0)
+        assert float((ref - gx).abs().max()) < 1e-5

@@ -1119,6 +1119,18 @@ __global__ void __launch_bounds__(256) segment_colsum_kernel(const void* __restr
 // 72 us for 25 216 x 512), with the image / position counters stepped, not divided, per row
 constexpr int RDG_RB = 32;
 constexpr int RDG_U = 8;  // rows whose loads are in flight together
+// The three f32 roundings of (dx + s * g) * gp as torch's f32 operators perform them. HIP's __fmul_rn / __fadd_rn are the
+// plain operators, which -ffp-contract=fast fuses into one fma (one rounding, and a last-bit difference in the bf16
+// result from the per-op path): contraction is switched off for these two functions instead
+__device__ __forceinline__ float rdg_scale(float s, float g) {
+#pragma clang fp contract(off)
+  return s * g;
+}
+__device__ __forceinline__ float rdg_gate(float dx, float sg, float gp) {
+#pragma clang fp contract(off)
+  const float v = dx + sg;
+  return v * gp;
+}
 __global__ void __launch_bounds__(256) router_dx_gate_kernel(const float* __restrict__ dx, long ldx,
                                                              const float* __restrict__ g, long ldg, float g_scale,
                                                              const bf16_t* __restrict__ gp, long ldgp, long T, long N,
@@ -1150,11 +1162,11 @@ __global__ void __launch_bounds__(256) router_dx_gate_kernel(const float* __rest
           dv[k] = *reinterpret_cast<const float2*>(d);
           if (pos >= reserve) {
             const float2 gg = *reinterpret_cast<const float2*>(gr);
-            gv[k] = float2{__fmul_rn(g_scale, gg.x), __fmul_rn(g_scale, gg.y)};
+            gv[k] = float2{rdg_scale(g_scale, gg.x), rdg_scale(g_scale, gg.y)};
           }
         } else {
           dv[k].x = d[0];
-          if (pos >= reserve) gv[k].x = __fmul_rn(g_scale, gr[0]);
+          if (pos >= reserve) gv[k].x = rdg_scale(g_scale, gr[0]);
         }
         gu[k] = *reinterpret_cast<const unsigned*>(gp + (t + k) * ldgp + c);
       }
@@ -1168,8 +1180,8 @@ __global__ void __launch_bounds__(256) router_dx_gate_kernel(const float* __rest
       if (t + k >= r1) break;
       unsigned o = 0u;
       if (ok[k]) {
-        const bf16_t o0 = f2bf(__fmul_rn(__fadd_rn(dv[k].x, gv[k].x), bf2f((bf16_t)(gu[k] & 0xffff))));
-        const bf16_t o1 = c1v ? f2bf(__fmul_rn(__fadd_rn(dv[k].y, gv[k].y), bf2f((bf16_t)(gu[k] >> 16)))) : (bf16_t)0;
+        const bf16_t o0 = f2bf(rdg_gate(dv[k].x, gv[k].x, bf2f((bf16_t)(gu[k] & 0xffff))));
+        const bf16_t o1 = c1v ? f2bf(rdg_gate(dv[k].y, gv[k].y, bf2f((bf16_t)(gu[k] >> 16)))) : (bf16_t)0;
         a0 += bf2f(o0);
         a1 += bf2f(o1);
         o = (unsigned)o0 | ((unsigned)o1 << 16);
@@ -1220,9 +1232,8 @@ __global__ void __launch_bounds__(256) router_dx_gate_pair_kernel(const float* _
     for (int k = 0; k < RDG_U; ++k) {
       if (t + k >= r1) break;
       const bool ok = t + k < T;
-      // (no fma contraction: the same two roundings as (dx + s * g) * gp in f32 elsewhere)
-      const bf16_t o0 = f2bf(__fmul_rn(__fadd_rn(dv[k].x, __fmul_rn(gs[k], gg[k].x)), bf2f((bf16_t)(gu[k] & 0xffff))));
-      const bf16_t o1 = f2bf(__fmul_rn(__fadd_rn(dv[k].y, __fmul_rn(gs[k], gg[k].y)), bf2f((bf16_t)(gu[k] >> 16))));
+      const bf16_t o0 = f2bf(rdg_gate(dv[k].x, rdg_scale(gs[k], gg[k].x), bf2f((bf16_t)(gu[k] & 0xffff))));
+      const bf16_t o1 = f2bf(rdg_gate(dv[k].y, rdg_scale(gs[k], gg[k].y), bf2f((bf16_t)(gu[k] >> 16))));
       const unsigned o = ok ? ((unsigned)o0 | ((unsigned)o1 << 16)) : 0u;
       if (ok) {
         a0 += bf2f(o0);

@@ -281,6 +281,10 @@ extern "C" int vit_layernorm_bwd(const void* dy, int64_t lddy, int32_t dy_f32, c
   VIT_CHECK_ARG(dy && x && mean && rstd && gamma && dx && partial, "vit_layernorm_bwd: null pointer");
   const DropDev drop = make_drop(dx_dropout);
   VIT_CHECK_ARG(D > 0 && D % 4 == 0 && D <= 2048, "vit_layernorm_bwd: D=%lld unsupported", (long long)D);
+  // every row is read and written in 16-B (f32) / 8-B (bf16) vectors
+  VIT_CHECK_ARG(lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && (!dres || lddres % 4 == 0) &&
+                    (!dx_bf16 || lddxb % 4 == 0),
+                "vit_layernorm_bwd: strides must be multiples of 4");
   if (rows <= 0) return VIT_OK;
   const int64_t nblk = ln_bwd_blocks(rows);
   hipStream_t s = (hipStream_t)stream;

@@ -431,7 +431,7 @@ def router_dx_gate_partial_rows(rows_pad):
 
 def router_dx_gate(dx, ldx, g, ldg, g_scale, gp, ldgp, T, N, reserve, cols, out, ldo, col_partial=None, ldp=0):
     """out (bf16 [rows_pad][cols_pad]) = bf16((dx + [t % N >= reserve] g_scale g[t // N]) * gp) on [T][cols], zeros
-    in the padding; col_partial: per 64-row block column sums of the rounded values (vit_router_dx_gate)"""
+    in the padding; col_partial: per 32-row block column sums of the rounded values (vit_router_dx_gate)"""
     _chk(dx, F32, "dx")
     _chk(g, F32, "g")
     _chk(gp, BF16, "gp")
