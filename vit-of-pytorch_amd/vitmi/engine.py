@@ -22,9 +22,10 @@ from dataclasses import dataclass
 
 import torch
 
-from . import ops
+from . import ops, wgrad
 from ._lib import (EPI_BF16, EPI_BIAS_BF16, EPI_BIAS_GELU_DGELU, EPI_BIAS_RESID_F32, EPI_MUL_BF16, EPI_PATCH,
-                   EPI_SPLITK, K_CONTIG, MN_CONTIG)
+                   K_CONTIG, MN_CONTIG)
+from .wgrad import Spec
 
 ALIGN = 64  # elements; every parameter starts 256-B aligned in the flat buffers
 
@@ -290,6 +291,58 @@ class _BiasReducer:
                     seg=D)
 
 
+class _WgradQueue:
+    """The weight gradients of one backward, each named once as a vitmi.wgrad Spec over K = the padded token rows.
+    defer > 0: a spec the table takes (M, N >= 256) is recorded and every `defer` layers' worth runs as one table launch
+    (direct at split 1: no slabs, no reductions), the rest at finish(); any other spec runs at once on the single form.
+    defer == 0: with `group`, a spec pushed with hold=True shares the next push's launch (a layer's out-projection and
+    q|k|v: one wave instead of two short grids); every other spec runs at once on the single form.
+    Launches go through `on_side` (the side stream under ViTEngine.overlap_wgrad); a spec's `done` runs once the launch
+    that reads its operands is issued (the backward's buffer releases)."""
+
+    def __init__(self, eng, K, on_side, defer, group):
+        self.eng, self.K, self.on_side, self.defer, self.group = eng, K, on_side, defer, group
+        self.recorded, self.layers, self.launches = [], 0, 0  # deferred: (spec, done) of the next table launch
+        self.held = []                                        # grouped: (spec, done) waiting for the next push
+
+    def _run(self, form, specs, *args, K=None, done=()):
+        eng = self.eng
+        self.on_side(lambda: form(specs, K or self.K, *args, alloc=eng._workspace, target=_WGRAD_TARGET,
+                                  probe=eng.probe_wgrad))
+        for fn in filter(None, done):
+            fn()
+
+    def single(self, spec, K=None, done=None):
+        """launch now, on its own (K: the cls-row gradients' own row count)"""
+        self._run(wgrad.single, spec, K=K, done=(done,))
+
+    def push(self, spec, done=None, hold=False):
+        if self.defer:
+            if spec.M >= 256 and spec.N >= 256:
+                self.recorded.append((spec, done))
+            else:
+                self.single(spec, done=done)
+        elif self.group and (hold or self.held):
+            self.held.append((spec, done))
+            if not hold:
+                (specs, dones), self.held = zip(*self.held), []
+                self._run(wgrad.group, specs, True, done=dones)
+        else:
+            self.single(spec, done=done)
+
+    def end_layer(self, i):
+        self.layers += 1
+        if self.layers == self.defer and i > 0:  # (layer 0's launch also takes the patch embedding's gradient)
+            self.finish()
+
+    def finish(self):
+        recorded, self.recorded, self.layers = self.recorded, [], 0
+        if recorded:
+            specs, dones = zip(*recorded)
+            self._run(wgrad.table, specs, self.eng._wgrad_tables, (self.eng._last_b, self.launches), done=dones)
+            self.launches += 1
+
+
 class ViTEngine:
     """Owns flat parameter/gradient buffers, the bf16 mirror and per-batch activations."""
 
@@ -349,7 +402,7 @@ class ViTEngine:
         # VITMI_WGRAD_DEFER: 0 = the per-layer path, N > 0 = layers per launch, "all" (default) = one launch.
         v = os.environ.get("VITMI_WGRAD_DEFER", "all")
         self.wgrad_defer = L if v == "all" else int(v)
-        self._wgrad_tables = {}  # (batch size, launch of the backward, first member) -> (member key, GemmGroupTable)
+        self._wgrad_tables = {}  # ((batch size, launch of the backward), first member) -> wgrad.table's entry
         # Only the cls token of the last layer's output reaches the classifier (src/model.py:210),
         # so that layer's out-projection, LayerNorm 2 and MLP (forward and backward) run on the b cls
         # rows and its attention on the first 32-query pair of each (image, head) (q_rows = 1); the
@@ -429,106 +482,10 @@ class ViTEngine:
             self._acts[b] = a
         return a
 
-    def _splitk(self, M, N, K, z=1):
-        """split-K factor for a weight-gradient GEMM (K = tokens) on the 256x256 ping-pong tile (one
-        workgroup per CU): ops.splitk_factor over _WGRAD_TARGET CUs (tools/gemm_bench.py: fc1/fc2 wgrad
-        at split 7 = 36 x 7 = 252 workgroups)."""
-        return ops.splitk_factor(M, N, K, z, _WGRAD_TARGET)
-
     def _workspace(self, numel):
         if self._ws is None or self._ws.numel() < numel:
             self._ws = torch.empty(numel, device=self.dev)
         return self._ws
-
-    def _wgrad(self, A, lda, B, ldb, M, N, K, out, ldo, batch=1, b_bs=0, out_bs=0):
-        """out[z] (f32, [M][N], ld ldo) = sum_t A[t][m] B[t][n]  (both operands K-major): split-K f32
-        slabs, then their fixed-order reduction (vit_splitk_reduce), both on the calling stream."""
-        s = self._splitk(M, N, K, batch)
-        ws = self._workspace(batch * s * M * N)
-        if self.probe_wgrad is not None:  # bench.py's roofline kernel: events on the stream it runs on
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        ops.gemm(A, B, ws, M, N, K, a_layout=MN_CONTIG, b_layout=MN_CONTIG, lda=lda, ldb=ldb, ldc=N,
-                 epilogue=EPI_SPLITK, batch=batch, b_bs=b_bs, split_k=s)
-        if self.probe_wgrad is not None:
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev1.record()
-            self.probe_wgrad.append((ev0, ev1, 2.0 * M * N * K * batch, K, False))
-        ops.splitk_reduce(ws, batch, s, M, N, out, ldo, out_bs)
-
-    def _wgrad_group(self, specs):
-        """Several _wgrad calls over the same K (token rows) as ONE split-K launch (ops.gemm_splitk_group) at a
-        common split (ops.splitk_factor_group), then each member's fixed-order reduction. specs: [(A, lda, B, ldb,
-        M, N, K, out, ldo, batch, b_bs, out_bs)]. Each output equals its _wgrad's up to the split (same slabs
-        summed in the same order when the splits agree)."""
-        K = specs[0][6]
-        assert all(sp[6] == K for sp in specs)
-        s = ops.splitk_factor_group([(sp[4], sp[5], sp[9]) for sp in specs], K, _WGRAD_TARGET)
-        sizes = [sp[9] * s * sp[4] * sp[5] for sp in specs]
-        ws = self._workspace(sum(sizes))
-        members, views, o = [], [], 0
-        for sp, n in zip(specs, sizes):
-            A, lda, B, ldb, M, N, _, _, _, batch, b_bs, _ = sp
-            w = ws[o:o + n]
-            o += n
-            views.append(w)
-            members.append((A, B, w, M, N, K, dict(a_layout=MN_CONTIG, b_layout=MN_CONTIG, lda=lda, ldb=ldb, ldc=N,
-                                                    epilogue=EPI_SPLITK, batch=batch, b_bs=b_bs, split_k=s)))
-        if self.probe_wgrad is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        ops.gemm_splitk_group(members)
-        if self.probe_wgrad is not None:
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev1.record()
-            self.probe_wgrad.append((ev0, ev1, sum(2.0 * sp[4] * sp[5] * K * sp[9] for sp in specs), K, True))
-        ops.splitk_reduce_group([(w, sp[9], s, sp[4], sp[5], sp[7], sp[8], sp[11], False) for sp, w in zip(specs, views)])
-
-    def _wgrad_batch(self, specs, slot):
-        """Deferred weight gradients (specs as for _wgrad_group, all over the same K) as one launch per
-        ops.GEMM_TABLE_MAX members. At the common split 1 (the usual case: a backward's worth of tiles covers the
-        CUs several times) every member writes its gradient directly; otherwise slabs and their fixed-order
-        reduction as in _wgrad_group. The device table is rebuilt only when the member list changes (engine
-        buffers are persistent: once per batch size); `slot` names this launch within the backward."""
-        K = specs[0][6]
-        assert all(sp[6] == K for sp in specs)
-        s = ops.splitk_factor_group([(sp[4], sp[5], sp[9]) for sp in specs], K, _WGRAD_TARGET)
-        views = None
-        if s > 1:
-            sizes = [sp[9] * s * sp[4] * sp[5] for sp in specs]
-            ws = self._workspace(sum(sizes))
-            views, o = [], 0
-            for n in sizes:
-                views.append(ws[o:o + n])
-                o += n
-        for c0 in range(0, len(specs), ops.GEMM_TABLE_MAX):
-            part = specs[c0:c0 + ops.GEMM_TABLE_MAX]
-            key = (s, self._ws.data_ptr() if s > 1 else 0) + tuple(
-                (sp[0].data_ptr(), sp[1], sp[2].data_ptr(), sp[3], sp[4], sp[5], sp[7].data_ptr()) + tuple(sp[8:])
-                for sp in part)
-            ent = self._wgrad_tables.get((self._last_b, slot, c0))
-            if ent is None or ent[0] != key:
-                members = []
-                for k, (A, lda, B, ldb, M, N, _, out, ldo, batch, b_bs, out_bs) in enumerate(part):
-                    kw = dict(a_layout=MN_CONTIG, b_layout=MN_CONTIG, lda=lda, ldb=ldb, epilogue=EPI_SPLITK, batch=batch,
-                              b_bs=b_bs, split_k=s)
-                    if s == 1:
-                        members.append((A, B, out, M, N, K, dict(kw, ldc=ldo, c_bs=out_bs), True))
-                    else:
-                        members.append((A, B, views[c0 + k], M, N, K, dict(kw, ldc=N), False))
-                ent = (key, ops.GemmGroupTable(members))
-                self._wgrad_tables[(self._last_b, slot, c0)] = ent
-            if self.probe_wgrad is not None:
-                ev0 = torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            ent[1].launch()
-            if self.probe_wgrad is not None:
-                ev1 = torch.cuda.Event(enable_timing=True)
-                ev1.record()
-                self.probe_wgrad.append((ev0, ev1, sum(2.0 * sp[4] * sp[5] * K * sp[9] for sp in part), K, True))
-        if s > 1:
-            ops.splitk_reduce_group([(w, sp[9], s, sp[4], sp[5], sp[7], sp[8], sp[11], False)
-                                     for sp, w in zip(specs, views)])
 
     # ---- forward -------------------------------------------------------------------------------
     def _dd(self, site, row_stride=1):
@@ -587,16 +544,9 @@ class ViTEngine:
                      ldaux=D, dropout=dd(1 + 3 * i))
             ops.layernorm_fwd(a.hm[i], D, f[ln("norm2.weight"):], f[ln("norm2.bias"):], a.ln2[i], D, a.mu2[i],
                               a.rs2[i], T, D)
-            if self.probe is not None:
-                ev0 = torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            ops.gemm(a.ln2[i], mv[ln("mlp.fc1.weight"):], a.gp[i], T, M, D, a_layout=K_CONTIG, b_layout=K_CONTIG,
-                     lda=D, ldb=D, ldc=M, epilogue=EPI_BIAS_GELU_DGELU, bias=f[ln("mlp.fc1.bias"):], C2=a.g[i],
-                     ldc2=M, dropout=dd(2 + 3 * i))
-            if self.probe is not None:
-                ev1 = torch.cuda.Event(enable_timing=True)
-                ev1.record()
-                self.probe.append((ev0, ev1))
+            wgrad.timed(self.probe, (), ops.gemm, a.ln2[i], mv[ln("mlp.fc1.weight"):], a.gp[i], T, M, D,
+                        a_layout=K_CONTIG, b_layout=K_CONTIG, lda=D, ldb=D, ldc=M, epilogue=EPI_BIAS_GELU_DGELU,
+                        bias=f[ln("mlp.fc1.bias"):], C2=a.g[i], ldc2=M, dropout=dd(2 + 3 * i))
             ops.gemm(a.g[i], mv[ln("mlp.fc2.weight"):], a.h[i + 1], T, D, M, a_layout=K_CONTIG, b_layout=K_CONTIG,
                      lda=M, ldb=M, ldc=D, epilogue=EPI_BIAS_RESID_F32, bias=f[ln("mlp.fc2.bias"):], aux=a.hm[i],
                      ldaux=D, dropout=dd(3 + 3 * i))
@@ -628,7 +578,7 @@ class ViTEngine:
         ops.gemm(a.c_g, mv[ln("mlp.fc2.weight"):], a.h[i + 1], b, D, M, a_layout=K_CONTIG, b_layout=K_CONTIG,
                  lda=M, ldb=M, ldc=S, epilogue=EPI_BIAS_RESID_F32, bias=f[ln("mlp.fc2.bias"):], aux=a.hm[i], ldaux=S)
 
-    def _backward_last_cls(self, a, i, b, g, on_side, bias):
+    def _backward_last_cls(self, a, i, b, g, wq, bias):
         """Backward of _forward_last_cls: the gradient reaching the last layer's output is non-zero on
         the cls rows only (a.c_dh, from the final LayerNorm backward), so fc2 / fc1 (data and weight
         gradients), LayerNorm 2 and the out-projection run on those b rows (weight-gradient K = the
@@ -640,7 +590,7 @@ class ViTEngine:
         f, mv = self.flat, self.mirror
         gv = lambda name: g[self.off(self.lname(i, name)):]
         bp = a.bp
-        on_side(lambda: self._wgrad(a.c_dh, D, a.c_g, M, D, M, bp, gv("mlp.fc2.weight"), M))
+        wq.single(Spec(a.c_dh, D, a.c_g, M, D, M, gv("mlp.fc2.weight"), M), K=bp)
         gpart = bias.buf("gelu", a.gelu_parts)
         w2 = mv[self.off(self.lname(i, "mlp.fc2.weight")):]
         kw = dict(a_layout=K_CONTIG, b_layout=MN_CONTIG, lda=D, ldb=M, ldc=M, epilogue=EPI_MUL_BF16, aux=a.c_gp,
@@ -648,12 +598,12 @@ class ViTEngine:
         ops.gemm(a.c_dh, w2, a.c_dg, b, M, D, **kw)
         tiles_m = ops.gemm_partial_rows(a.c_dh, w2, a.c_dg, b, M, D, **kw)
         bias.reduce(gpart, tiles_m, M, M, (gv("mlp.fc1.bias"),))
-        on_side(lambda: self._wgrad(a.c_dg, M, a.c_ln2, D, M, D, bp, gv("mlp.fc1.weight"), D))
+        wq.single(Spec(a.c_dg, M, a.c_ln2, D, M, D, gv("mlp.fc1.weight"), D), K=bp)
         ops.gemm(a.c_dg, mv[self.off(self.lname(i, "mlp.fc1.weight")):], a.c_dyln, b, D, M, a_layout=K_CONTIG,
                  b_layout=MN_CONTIG, lda=M, ldb=D, ldc=D, epilogue=EPI_BF16)
         bias.ln_bwd(a.c_dyln, D, a.hm[i], S, a.c_mu2, a.c_rs2, f[self.off(self.lname(i, "norm2.weight")):], a.dh, S, b,
                     gv("norm2.weight"), gv("attn.out.bias"), dres=a.dh, lddres=S, dx_bf16=a.c_dh2, lddxb=D)
-        on_side(lambda: self._wgrad(a.c_o, D, a.c_dh2, D, D, D, bp, gv("attn.out.weight"), D))
+        wq.single(Spec(a.c_o, D, a.c_dh2, D, D, D, gv("attn.out.weight"), D), K=bp)
         ops.zero_(a.dO)
         ops.gemm(a.c_dh2, mv[self.off(self.lname(i, "attn.out.weight")):], a.dO, b, D, D, a_layout=K_CONTIG,
                  b_layout=K_CONTIG, lda=D, ldb=D, ldc=S, epilogue=EPI_BF16)
@@ -724,7 +674,7 @@ class ViTEngine:
 
         Deferred mode (wgrad_defer > 0, no grad_ready_hook, no overlap_wgrad): the full-token layers' weight
         gradients are only recorded, their operands kept in per-layer buffers (_Acts.defer_bufs), and run as
-        one batched launch per wgrad_defer layers (_wgrad_batch), the last one after the last data gradient."""
+        one batched launch per wgrad_defer layers (_WgradQueue), the last one after the last data gradient."""
         cfg = self.cfg
         b = self._last_b
         a = self.acts(b)
@@ -782,17 +732,9 @@ class ViTEngine:
         group = self.group_wgrad and D >= 256  # (the grouped kernel takes M, N >= 256)
         # deferred weight gradients (wgrad_defer layers per launch), unless something wants a layer's gradients early
         defer = self.wgrad_defer if not hook and not overlap and D >= 256 and M >= 256 else 0
-        pending, held, launches = [], 0, 0  # recorded specs, layers among them, launches issued
+        wq = _WgradQueue(self, a.Tp, on_side, defer, group)
         dhbs, dgs, dqkvs = a.defer_bufs() if defer else (a.dhb, a.dg, a.dqkv)
         nd = len(dhbs)
-
-        def flush_wgrad():
-            nonlocal pending, held, launches
-            if pending:
-                self._wgrad_batch(pending, launches)
-                launches += 1
-            pending, held = [], 0
-        out_wb = None  # dhb buffer of a deferred out-projection weight gradient (group)
         bias = _BiasReducer(self, a)
         # classifier head (f32): dWc = dl^T lncls, dbc = colsum(dl), dlncls = dl Wc
         ops.gemm_f32(C, D, b, dl, C, True, a.lncls, D, False, gv("classifier.weight"), D)
@@ -816,17 +758,14 @@ class ViTEngine:
             li = i % len(dgs)
             if pruned and i == L - 1:
                 # MLP, LayerNorm 2 and out-projection backward on the cls rows; dO = 0 elsewhere
-                self._backward_last_cls(a, i, b, g, on_side, bias)
+                self._backward_last_cls(a, i, b, g, wq, bias)
                 wb = (wb + 1) % nd
             else:
                 dhb = dhbs[wb]
                 # ---- MLP: h_{i+1} = hm + fc2(gelu(fc1(ln2(hm)))) ----
                 # (fc2 bias grad = column sums of dh, already produced by the LayerNorm backward above)
-                if defer:
-                    pending.append((dhb, D, a.g[i], M, D, M, a.Tp, gv(self.lname(i, "mlp.fc2.weight")), M, 1, 0, 0))
-                else:
-                    on_side(lambda: self._wgrad(dhb, D, a.g[i], M, D, M, a.Tp, gv(self.lname(i, "mlp.fc2.weight")), M))
-                release("dhb", wb)
+                wq.push(Spec(dhb, D, a.g[i], M, D, M, gv(self.lname(i, "mlp.fc2.weight")), M),
+                        done=lambda k=wb: release("dhb", k))
                 dg = dgs[li]
                 acquire("dg", li)
                 gpart = bias.buf("gelu", a.gelu_parts)
@@ -836,11 +775,8 @@ class ViTEngine:
                 ops.gemm(dhb, w2, dg, T, M, D, **kw)
                 tiles_m = ops.gemm_partial_rows(dhb, w2, dg, T, M, D, **kw)
                 bias.reduce(gpart, tiles_m, M, M, (gv(self.lname(i, "mlp.fc1.bias")),))
-                if defer:
-                    pending.append((dg, M, a.ln2[i], D, M, D, a.Tp, gv(self.lname(i, "mlp.fc1.weight")), D, 1, 0, 0))
-                else:
-                    on_side(lambda: self._wgrad(dg, M, a.ln2[i], D, M, D, a.Tp, gv(self.lname(i, "mlp.fc1.weight")), D))
-                release("dg", li)
+                wq.push(Spec(dg, M, a.ln2[i], D, M, D, gv(self.lname(i, "mlp.fc1.weight")), D),
+                        done=lambda k=li: release("dg", k))
                 ops.gemm(dg, mv[ln("mlp.fc1.weight"):], a.dyln, T, D, M, a_layout=K_CONTIG, b_layout=MN_CONTIG, lda=M,
                          ldb=D, ldc=D, epilogue=EPI_BF16)
                 wb = (wb + 1) % nd
@@ -850,14 +786,9 @@ class ViTEngine:
                             gv(self.lname(i, "norm2.weight")), gv(self.lname(i, "attn.out.bias")),
                             dres=a.dh, lddres=D, dx_bf16=dhb, lddxb=D, dx_dropout=dd(1 + 3 * i))
                 # ---- attention: hm = h + out(attn(ln1(h))) ----
-                out_spec = (a.o[i], D, dhb, D, D, D, a.Tp, gv(self.lname(i, "attn.out.weight")), D, 1, 0, 0)
-                if defer:
-                    pending.append(out_spec)
-                elif group:  # launched with the q|k|v weight gradient below (dhb stays intact until then)
-                    out_wb = wb
-                else:
-                    on_side(lambda: self._wgrad(*out_spec[:9]))
-                    release("dhb", wb)
+                # (grouped: launched with the q|k|v weight gradient below, dhb stays intact until then)
+                wq.push(Spec(a.o[i], D, dhb, D, D, D, gv(self.lname(i, "attn.out.weight")), D),
+                        done=lambda k=wb: release("dhb", k), hold=True)
                 ops.gemm(dhb, mv[ln("attn.out.weight"):], a.dO, T, D, D, a_layout=K_CONTIG, b_layout=K_CONTIG, lda=D,
                          ldb=D, ldc=D, epilogue=EPI_BF16)
             dqkv = dqkvs[li]
@@ -869,22 +800,11 @@ class ViTEngine:
             zs = ln("attn.key.weight") - qo
             qb = ln("attn.query.bias")
             bias.reduce(qpart, b * a.attn_bias_rows, 3 * D, 3 * D, (g[qb:], g[qb + zs:], g[qb + 2 * zs:]), seg=D)
-            qkv_spec = (a.ln1[i], D, dqkv, 3 * D, D, D, a.Tp, g[qo:], D, 3, D, zs)
-            if defer:
-                pending.append(qkv_spec)
-                held += 1
-                if held == defer and i > 0:  # (layer 0's launch also takes the patch embedding's gradient)
-                    flush_wgrad()
-            elif out_wb is not None:
-                # the out-projection (9 tiles at B/16) and q|k|v (27) weight gradients as one grid: one wave of
-                # 252 workgroups at split 7 instead of 252 short ones (split 28) and 243 (split 9)
-                on_side(lambda: self._wgrad_group([out_spec, qkv_spec]))
-                release("dqkv", li)
-                release("dhb", out_wb)
-                out_wb = None
-            else:
-                on_side(lambda: self._wgrad(*qkv_spec[:9], batch=3, b_bs=D, out_bs=zs))
-                release("dqkv", li)
+            # grouped with a held out-projection: its 9 tiles (at B/16) and q|k|v's 27 as one grid, one wave of 252
+            # workgroups at split 7 instead of 252 short ones (split 28) and 243 (split 9)
+            wq.push(Spec(a.ln1[i], D, dqkv, 3 * D, D, D, g[qo:], D, batch=3, b_bs=D, out_bs=zs),
+                    done=lambda k=li: release("dqkv", k))
+            wq.end_layer(i)
             ops.gemm(dqkv, self.wqkv[i], a.dyln, T, D, 3 * D, a_layout=K_CONTIG, b_layout=K_CONTIG, lda=3 * D,
                      ldb=3 * D, ldc=D, epilogue=EPI_BF16)
             wb = (wb + 1) % nd
@@ -895,13 +815,8 @@ class ViTEngine:
                         dx_dropout=dd(3 + 3 * (i - 1)) if i > 0 else dd(0))
             fire(self.layout.buckets[L - i])
         # ---- embedding: conv weight grad (wgrad over patches), bias / pos / cls ----
-        dhb = dhbs[wb]
-        if defer and cfg.patch_k >= 256:
-            pending.append((dhb, D, a.patches, a.kpad, D, cfg.patch_k, a.Tp, gv("embedding.weight"), cfg.patch_k, 1, 0, 0))
-        else:
-            on_side(lambda: self._wgrad(dhb, D, a.patches, a.kpad, D, cfg.patch_k, a.Tp, gv("embedding.weight"),
-                                        cfg.patch_k))
-        flush_wgrad()  # after the last data gradient; the bias and column reductions follow
+        wq.push(Spec(dhbs[wb], D, a.patches, a.kpad, D, cfg.patch_k, gv("embedding.weight"), cfg.patch_k))
+        wq.finish()  # after the last data gradient; the bias and column reductions follow
         ops.embed_grad(a.dh, b, N, D, gv("transformer.pos_embedding.pos_embedding"), gv("cls_token"),
                        gv("embedding.bias"), dropout=dd(0))
         fire(self.layout.buckets[-1])

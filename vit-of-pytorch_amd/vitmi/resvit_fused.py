@@ -31,19 +31,14 @@ import os
 import torch
 
 from . import flat as _flat
-from . import ops
+from . import ops, wgrad
 from ._lib import (EPI_BF16, EPI_BIAS_BF16, EPI_BIAS_GELU_DGELU, EPI_BIAS_RESID_F32, EPI_F32, EPI_MUL_BF16,
-                   EPI_PATCH, EPI_SPLITK, K_CONTIG, MN_CONTIG)
+                   EPI_PATCH, K_CONTIG, MN_CONTIG)
+from .functional import _pad_bf16, _rup, _zero_row
+from .wgrad import Spec
 
 BF16, F32 = torch.bfloat16, torch.float32
 KX = 64  # extra K columns of the q|k|v operand (LoRA down-projections, zero padded)
-
-
-def _rup(x, m):
-    return (x + m - 1) // m * m
-
-
-_ZROW = {}
 
 
 def _alloc_pad(rows_p, cols_p, rows, cols, dev, dtype=BF16):
@@ -59,14 +54,6 @@ def _alloc_pad(rows_p, cols_p, rows, cols, dev, dtype=BF16):
     if cols_p > cols and rows:
         out[:rows, cols:].zero_()
     return out
-
-
-def _zero_row(n, dev):
-    z = _ZROW.get(dev)
-    if z is None or z.numel() < n:
-        z = torch.zeros(max(n, 4096), device=dev, dtype=F32)
-        _ZROW[dev] = z
-    return z
 
 
 def supported(block):
@@ -296,32 +283,22 @@ class _FusedLayer(torch.autograd.Function):
                  epilogue=EPI_BF16, batch=3, a_bs=D, b_bs=D * r8, c_bs=r8)
         need = ctx.needs_input_grad
         # dB_z and dA_z (batched over z): one grouped split-K launch and one grouped reduction, each at the split
-        # ops.wgrad would give it alone (bit-identical sums)
-        dB = torch.empty(3, D, r, device=dev)
+        # ops.wgrad would give it alone (bit-identical sums). Each factor's gradient goes straight into its flat .grad
+        # view where it has one (no AccumulateGrad add), else into dA[z] / dB[z]
         dA = torch.empty(3, r, D, device=dev)
-        sB, sA = ops.splitk_factor(D, r, Tp, 3), ops.splitk_factor(r, D, Tp, 3)
-        wsB = torch.empty(3 * sB * D * r, device=dev)
-        wsA = torch.empty(3 * sA * r * D, device=dev)
-        kw = dict(a_layout=MN_CONTIG, b_layout=MN_CONTIG, epilogue=EPI_SPLITK, batch=3)
-        ops.gemm_splitk_group([(dqkv, a1[:, D:], wsB, D, r, Tp, dict(kw, lda=3 * D, ldb=Kq, ldc=r, a_bs=D, b_bs=r8,
-                                                                      split_k=sB)),
-                               (v_all, a1, wsA, r, D, Tp, dict(kw, lda=KX, ldb=Kq, ldc=D, a_bs=r8, split_k=sA))])
-        # each factor's gradient straight into its flat .grad view where it has one (no AccumulateGrad add), else
-        # into dA / dB
-        marks, jobs, grads = [], [], []
+        dB = torch.empty(3, D, r, device=dev)
+        marks, grads, dsts, accs = [], [], ([], []), ([], [])
         for z in range(3):
-            for ws_, s_, M_, N_, full, p_, nd in ((wsA, sA, r, D, dA, ctx.lora[2 * z], need[1 + 2 * z]),
-                                                   (wsB, sB, D, r, dB, ctx.lora[2 * z + 1], need[2 + 2 * z])):
-                slab = ws_[z * s_ * M_ * N_:(z + 1) * s_ * M_ * N_]
+            for j, full in enumerate((dA, dB)):
+                p_, nd = ctx.lora[2 * z + j], need[1 + 2 * z + j]
                 sk = _flat.grad_sink(p_, nd) if LORA_SINK else None
                 if sk is not None:
-                    jobs.append((slab, 1, s_, M_, N_, sk, N_, 0, True))
                     marks.append(p_)
-                    grads.append(None)
-                else:
-                    jobs.append((slab, 1, s_, M_, N_, full[z], N_, 0, False))
-                    grads.append(full[z] if nd else None)
-        ops.splitk_reduce_group(jobs)
+                dsts[j].append(full[z] if sk is None else sk)
+                accs[j].append(sk is not None)
+                grads.append(full[z] if sk is None and nd else None)
+        wgrad.group([Spec(dqkv, 3 * D, a1[:, D:], Kq, D, r, dsts[1], r, batch=3, a_bs=D, b_bs=r8, accumulate=accs[1]),
+                     Spec(v_all, KX, a1, Kq, r, D, dsts[0], D, batch=3, a_bs=r8, accumulate=accs[0])], Tp, common=False)
         # q|k|v data gradient: dqkv W_qkv + v A (f32), then LN1 backward with the residual gradient
         dy1 = torch.empty(T, D, device=dev)
         ops.gemm(v_all, a_all, dy1, T, D, KX, a_layout=K_CONTIG, b_layout=MN_CONTIG, lda=KX, ldb=D, ldc=D,
@@ -621,7 +598,8 @@ class _ApproxStep(torch.autograd.Function):
         # dWd [r][D] = dh^T x and dWu [D][r] = dout^T h: one grouped split-K launch (each alone is 3 tiles, under a
         # wave at any split)
         marks, need = [], (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        wg = [m for m, nd in zip(((dhb, rk, xb, kp, r, D, 0), (db, kp, hb, rk, D, r, 1)), need) if nd]
+        wg = [m for m, nd in zip(((0, Spec(dhb, rk, xb, kp, r, D, None, D)), (1, Spec(db, kp, hb, rk, D, r, None, r))),
+                                 need) if nd]
         g = _finish_grads(rp, wg, [], ctx.params, (True, True), marks, dev, own_split=True)
         _sunk(marks)
         return dx, g.get(0), g.get(1), None
@@ -652,16 +630,6 @@ def _pad_bf16_many(items):
     return outs
 
 
-def _pad_bf16(x2, rows_p, cols_p):
-    rows, cols = x2.shape
-    out = torch.empty(rows_p, cols_p, device=x2.device, dtype=BF16)
-    if rows:
-        ops.cast_pad_rows(x2, rows, cols, out, cols_p)
-    if rows_p > rows:
-        ops.zero_(out[rows:])
-    return out
-
-
 def _colsum(x, rows, cols, ld, p=None, need=True, marks=None):
     """column sums of x (a bias gradient); with p: accumulated in place into p's flat .grad view when it has
     one (vitmi.flat.grad_sink: p appended to marks, None returned)"""
@@ -673,19 +641,6 @@ def _colsum(x, rows, cols, ld, p=None, need=True, marks=None):
         return None
     out = torch.empty(cols, device=x.device, dtype=F32)
     ops.colsum(x, rows, cols, ld, part, out)
-    return out
-
-
-def _wgrad(A, lda, B, ldb, M, N, K, p=None, need=True, marks=None):
-    """weight gradient [M][N] = A^T B (ops.wgrad), accumulated into p's flat .grad view in place when it has one
-    (as _colsum); else a new f32 tensor. With the view, no AccumulateGrad add runs for p."""
-    sk = _flat.grad_sink(p, need) if p is not None else None
-    if sk is not None:
-        ops.wgrad(A, lda, B, ldb, M, N, K, sk, N, accumulate=True)
-        marks.append(p)
-        return None
-    out = torch.empty(M, N, device=A.device, dtype=F32)
-    ops.wgrad(A, lda, B, ldb, M, N, K, out, N)
     return out
 
 
@@ -754,9 +709,9 @@ def _dgrad_f32(dyb, wpad, ldw, n_in, T):
 
 
 def _finish_grads(K, wgrads, biases, params, need, marks, dev, own_split=False):
-    """The weight and bias gradients of a router backward, all at once: wgrads [(A, lda, B, ldb, M, N, i)] are
-    [M][N] = A^T B over the same K (padded token) rows, as ONE split-K launch (ops.gemm_splitk_group) at a common
-    split (own_split: each member at the split ops.wgrad would give it alone, so its sums are bit-identical to
+    """The weight and bias gradients of a router backward, all at once: wgrads [(i, wgrad.Spec without destination)]
+    are [M][N] = A^T B over the same K (padded token) rows, as ONE split-K launch (wgrad.group) at a common split
+    (own_split: each member at the split ops.wgrad would give it alone, so its sums are bit-identical to
     ops.wgrad's) and each member's fixed-order reduction; biases [(partials f32 [rows][cols], rows, cols, i)] are
     column sums of GEMM / gate partials, ONE vit_colsum_batch launch. i indexes params / need; a gradient goes to
     the parameter's flat .grad view in place when it has one (vitmi.flat.grad_sink: parameter appended to marks,
@@ -775,24 +730,11 @@ def _finish_grads(K, wgrads, biases, params, need, marks, dev, own_split=False):
         return t, False
 
     if wgrads:
-        if own_split:
-            ss = [ops.splitk_factor(M, N, K) for (_, _, _, _, M, N, _) in wgrads]
-        else:
-            ss = [ops.splitk_factor_group([(M, N, 1) for (_, _, _, _, M, N, _) in wgrads], K)] * len(wgrads)
-        ws = torch.empty(sum(s * M * N for s, (_, _, _, _, M, N, _) in zip(ss, wgrads)), device=dev, dtype=F32)
-        members, views, o = [], [], 0
-        for s, (A, lda, B, ldb, M, N, _) in zip(ss, wgrads):
-            w = ws[o:o + s * M * N]
-            o += s * M * N
-            views.append(w)
-            members.append((A, B, w, M, N, K, dict(a_layout=MN_CONTIG, b_layout=MN_CONTIG, lda=lda, ldb=ldb, ldc=N,
-                                                    epilogue=EPI_SPLITK, split_k=s)))
-        ops.gemm_splitk_group(members)
-        jobs = []
-        for s, (_, _, _, _, M, N, i), w in zip(ss, wgrads, views):
-            d, acc = dst(i, (M, N))
-            jobs.append((w, 1, s, M, N, d, N, 0, acc))
-        ops.splitk_reduce_group(jobs)
+        specs = []
+        for i, sp in wgrads:
+            d, acc = dst(i, (sp.M, sp.N))
+            specs.append(sp._replace(out=d, accumulate=acc))
+        wgrad.group(specs, K, common=not own_split)
     jobs = []
     for part, rows, cols, i in biases:
         d, acc = dst(i, (cols,))
@@ -816,7 +758,8 @@ def _mlp_backward(d2, T, xb, acts, ws, w1, w2, w3, need_dx, params, need, marks)
     du2, (p2, r2) = _dgrad_mul(dlb, ws[2], h2p, H2, T, gp2, h2p)
     du1, (p1, r1) = _dgrad_mul(du2, ws[1], h1p, H1, T, gp1, h1p)
     dx = _dgrad_f32(du1, ws[0], kp, K1, T) if need_dx else None
-    wgrads = [(dlb, dlb.shape[1], g2, h2p, O, H2, 4), (du2, h2p, g1, h1p, H2, H1, 2), (du1, h1p, xb, kp, H1, K1, 0)]
+    wgrads = [(4, Spec(dlb, dlb.shape[1], g2, h2p, O, H2, None, H2)), (2, Spec(du2, h2p, g1, h1p, H2, H1, None, H1)),
+              (0, Spec(du1, h1p, xb, kp, H1, K1, None, K1))]
     biases = [(p2, r2, H2, 3), (p1, r1, H1, 1)]
     if O % 2 == 0:
         # the output bias gradient (column sums of the f32 dY [T][O], O = 2): 64-row segment sums, summed with the
@@ -952,7 +895,7 @@ class _RouterNet(torch.autograd.Function):
         ops.router_dx_gate(dxe, Hh, gsum, Hh, 1.0 / (N - reserve), gp0, h0p, T, N, reserve, Hh, du0b, h0p, p0, Hh)
         dln = _dgrad_f32(du0b, w0b, dp, D, T)
         # the mlp's members are indexed from 2 (w1 ..); in_conv's weight / bias are 0 / 1
-        wg = [(a, la, b_, lb, m, n, i + 2) for a, la, b_, lb, m, n, i in wg] + [(du0b, h0p, lnb, dp, Hh, D, 0)]
+        wg = [(i + 2, sp) for i, sp in wg] + [(0, Spec(du0b, h0p, lnb, dp, Hh, D, None, D))]
         bs = [(p_, r_, c_, i + 2) for p_, r_, c_, i in bs] + [(p0, r0, Hh, 1)]
         g = _finish_grads(rp, wg, bs, ctx.params, need, marks, dev)
         dx = torch.empty(T, D, device=dev, dtype=F32)
