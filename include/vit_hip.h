@@ -314,6 +314,28 @@ int vit_preprocess_u8_gather(const uint8_t* images, int64_t n_images, int32_t la
                              int64_t out_h, int64_t out_w, const float* mean_std, float* out,
                              const int64_t* labels_in, int64_t* labels_out, vit_stream_t stream);
 
+/* The same transform over decoded image files, whose sizes differ within one batch (ImageNet / TinyImageNet
+ * folders, src/data_loaders.py:96-124, res-vit/data_loaders.py:96-216: Resize((s, s)) of every image), in one
+ * launch: out[b] = transform(source image index[b]).
+ * bytes: n_bytes bytes of device memory holding the images end to end in any order, each uint8 HWC [H][W][3]
+ * (byte loads: no alignment is assumed). geom: device int64 [n_images][3], row i = (offset, H, W): image i starts
+ * at bytes + offset and has H x W pixels; rows may overlap or leave gaps. index: device int64 [B], any order,
+ * repeats allowed; NULL = image b (then B <= n_images, or the outputs past it are bad ones). flips: device uint8
+ * [B], indexed by the OUTPUT image b (NULL = no flips). Resize to (out_h, out_w), flip and normalisation are
+ * vit_preprocess_u8's, bit for bit, each image with its own two ratios: a block reads its image's row of geom and
+ * takes the tiled two-pass path when both axes have <= 9 taps (ratios up to 4x) and a per-pixel path otherwise.
+ * out f32 NCHW [B,3,out_h,out_w]; mean_std: host float[6]. labels_in (device int64 [n_images]) and labels_out
+ * (device int64 [B]): when both are non-NULL, labels_out[b] = labels_in[index[b]]; either NULL: not touched.
+ * Nothing is read through bad metadata: an index[b] outside [0, n_images), H or W <= 0 or >= 2^15, offset < 0 or
+ * offset + 3*H*W > n_bytes fill out[b] with NaN and set labels_out[b] = -1, for that output alone
+ * (vit_cross_entropy's rule for a bad label: the loss of such a step is NaN instead of silently wrong).
+ * bytes, geom, out or mean_std NULL; B <= 0, n_images <= 0, n_bytes <= 0 or an output size <= 0; out_h or out_w
+ * >= 2^15, B >= 2^31, B*out_h*out_w >= 2^40 or n_images >= 2^40: VIT_ERR_INVALID_ARG, nothing launched. */
+int vit_preprocess_u8_ragged(const uint8_t* bytes, int64_t n_bytes, const int64_t* geom, int64_t n_images,
+                             const int64_t* index, int64_t B, const uint8_t* flips, int64_t out_h, int64_t out_w,
+                             const float* mean_std, float* out, const int64_t* labels_in, int64_t* labels_out,
+                             vit_stream_t stream);
+
 /* token-level grads of the embedding (src/model.py:17,203-204): from dh0 f32 [B*N, D]:
  * dpos[n][d] = sum_b dh0[b*N+n][d]; dcls = dpos[0]; dconv_bias = sum_{n>=1} dpos[n].
  * dropout (optional): dh0 is taken through the position-embedding dropout's multipliers first. */

@@ -297,7 +297,231 @@ PrepArgs make_args(const uint8_t* images, int64_t B, int64_t H, int64_t W, int64
   return p;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// vit_preprocess_u8_ragged: the same transform over decoded image files, whose sizes differ within a batch
+// (src/data_loaders.py:100-112 ImageNet, res-vit/data_loaders.py:110-122,191-203: Resize((s, s)) of every image).
+// The images lie end to end in one byte array; geom[i] = (offset, H, W) says where image i is. A block owns the
+// same 64 x 32 output tile as the tiled kernel, reads its image's row of the table, refuses it when it does not
+// fit the array, derives both axes from it and picks its path - uniformly for the block, per image for the launch:
+//   <= 9 taps on both axes   the two-pass LDS scheme above with run-time tap counts, specialised for 3 / 5 / 9
+//                            (an upscaled, a <= 2x and a <= 4x image: the horizontal weights stay in registers);
+//   anything larger          one thread per output pixel. The column's horizontal weights are computed once per
+//                            block into the LDS the band does not need here (up to kBandMax taps, a ratio of
+//                            66; above that they are recomputed per use - the same expression, the same bits).
+struct RaggedArgs {
+  const uint8_t* bytes;
+  long n_bytes;
+  const int64_t* geom;  // [n_images][3] = offset, H, W
+  long n_images;
+  const int64_t* index;  // [B] or NULL = image b
+  long B;
+  const uint8_t* flips;
+  int oh, ow;
+  float mean[3], stdv[3];
+  float* out;
+  const int64_t* labels_in;
+  int64_t* labels_out;
+};
+
+// ceil(support) * 2 + 1 of axis_ksize, on the device
+__device__ inline int axis_ksize_dev(const Axis& a) { return (int)ceil(a.support) * 2 + 1; }
+
+template <int KMAX>
+__device__ inline void ragged_tiled(const RaggedArgs& p, const uint8_t* img, const Axis& ax, const Axis& ay, int b,
+                                    int y0, int rows, int (*s_ky)[9], int* s_ymin, int* s_ycnt,
+                                    uint32_t (*s_h)[kColsPerBlock]) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.y * kColsPerBlock + threadIdx.x;
+  if (tid < rows) {
+    int ymin, ycnt;
+    double yc, yw;
+    taps(ay, y0 + tid, ymin, ycnt, yc, yw);
+    s_ymin[tid] = ymin;
+    s_ycnt[tid] = ycnt;
+    for (int j = 0; j < KMAX; ++j) s_ky[tid][j] = j < ycnt ? coeff(ay, j, ymin, yc, yw) : 0;
+  }
+  const int x = blockIdx.x * kColsPerBlock + threadIdx.x;
+  const bool live = x < p.ow;
+  const int xs = live && p.flips && p.flips[b] ? p.ow - 1 - x : x;
+  int xmin = 0, xcnt = 0;
+  int kx[KMAX];
+  if (live) {
+    double xc, xw;
+    taps(ax, xs, xmin, xcnt, xc, xw);
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) kx[k] = k < xcnt ? coeff(ax, k, xmin, xc, xw) : 0;
+  }
+  __syncthreads();
+  const int band0 = s_ymin[0];
+  const int nband = s_ymin[rows - 1] + s_ycnt[rows - 1] - band0;  // <= kBandMax: both axes have <= 9 taps
+  const long row_bytes = (long)ax.in_size * 3;
+  if (live) {
+    const uint8_t* src = img + (long)band0 * row_bytes + (long)xmin * 3;
+    for (int r = threadIdx.y; r < nband; r += kRowLanes) {
+      const uint8_t* row = src + (long)r * row_bytes;
+      int h0 = 1 << (kPrecisionBits - 1), h1 = h0, h2 = h0;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if (k < xcnt) {
+          h0 += row[3 * k] * kx[k];
+          h1 += row[3 * k + 1] * kx[k];
+          h2 += row[3 * k + 2] * kx[k];
+        }
+      }
+      s_h[r][threadIdx.x] = (uint32_t)clip8(h0) | ((uint32_t)clip8(h1) << 8) | ((uint32_t)clip8(h2) << 16);
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  const long plane = (long)p.oh * p.ow;
+  float* o = p.out + (long)b * 3 * plane + x;
+  for (int r = threadIdx.y; r < rows; r += kRowLanes) {
+    const int ymin = s_ymin[r] - band0, ycnt = s_ycnt[r];
+    int acc0 = 1 << (kPrecisionBits - 1), acc1 = acc0, acc2 = acc0;
+    for (int j = 0; j < ycnt; ++j) {
+      const uint32_t hv = s_h[ymin + j][threadIdx.x];
+      const int cy = s_ky[r][j];
+      acc0 += (int)(hv & 0xffu) * cy;
+      acc1 += (int)((hv >> 8) & 0xffu) * cy;
+      acc2 += (int)((hv >> 16) & 0xffu) * cy;
+    }
+    const long off = (long)(y0 + r) * p.ow;
+    o[off] = ((float)clip8(acc0) / 255.0f - p.mean[0]) / p.stdv[0];
+    o[plane + off] = ((float)clip8(acc1) / 255.0f - p.mean[1]) / p.stdv[1];
+    o[2 * plane + off] = ((float)clip8(acc2) / 255.0f - p.mean[2]) / p.stdv[2];
+  }
+}
+
+// the per-pixel body for a block whose image has more than 9 taps on an axis; ksx = the horizontal kernel size
+__device__ inline void ragged_pixel(const RaggedArgs& p, const uint8_t* img, const Axis& ax, const Axis& ay, int ksx,
+                                    int b, int y0, int rows, uint32_t (*s_h)[kColsPerBlock]) {
+#pragma clang fp contract(off)
+  const int x = blockIdx.x * kColsPerBlock + threadIdx.x;
+  const bool live = x < p.ow;
+  const int xs = live && p.flips && p.flips[b] ? p.ow - 1 - x : x;
+  int xmin = 0, xcnt = 0;
+  double xc = 0.0, xw = 0.0;
+  if (live) taps(ax, xs, xmin, xcnt, xc, xw);
+  const bool held = ksx <= kBandMax;  // xcnt <= ksx: column threadIdx.x's weights fit s_h[.][threadIdx.x]
+  if (held) {
+    for (int k = threadIdx.y; k < xcnt; k += kRowLanes) s_h[k][threadIdx.x] = (uint32_t)coeff(ax, k, xmin, xc, xw);
+    __syncthreads();
+  }
+  if (!live) return;
+  const long plane = (long)p.oh * p.ow;
+  const long row_bytes = (long)ax.in_size * 3;
+  float* o = p.out + (long)b * 3 * plane + x;
+  for (int r = threadIdx.y; r < rows; r += kRowLanes) {
+    int ymin, ycnt;
+    double yc, yw;
+    taps(ay, y0 + r, ymin, ycnt, yc, yw);
+    int acc0 = 1 << (kPrecisionBits - 1), acc1 = acc0, acc2 = acc0;
+    for (int j = 0; j < ycnt; ++j) {
+      const uint8_t* row = img + (long)(ymin + j) * row_bytes + (long)xmin * 3;
+      int h0 = 1 << (kPrecisionBits - 1), h1 = h0, h2 = h0;
+      for (int k = 0; k < xcnt; ++k) {
+        const int c = held ? (int)s_h[k][threadIdx.x] : coeff(ax, k, xmin, xc, xw);
+        h0 += row[3 * k] * c;
+        h1 += row[3 * k + 1] * c;
+        h2 += row[3 * k + 2] * c;
+      }
+      const int cy = coeff(ay, j, ymin, yc, yw);
+      acc0 += clip8(h0) * cy;
+      acc1 += clip8(h1) * cy;
+      acc2 += clip8(h2) * cy;
+    }
+    const long off = (long)(y0 + r) * p.ow;
+    o[off] = ((float)clip8(acc0) / 255.0f - p.mean[0]) / p.stdv[0];
+    o[plane + off] = ((float)clip8(acc1) / 255.0f - p.mean[1]) / p.stdv[1];
+    o[2 * plane + off] = ((float)clip8(acc2) / 255.0f - p.mean[2]) / p.stdv[2];
+  }
+}
+
+__global__ void __launch_bounds__(kColsPerBlock* kRowLanes) preprocess_ragged_kernel(RaggedArgs p) {
+  __shared__ int s_ky[kRowsPerBlock][9];
+  __shared__ int s_ymin[kRowsPerBlock], s_ycnt[kRowsPerBlock];
+  __shared__ uint32_t s_h[kBandMax][kColsPerBlock];  // 34 KB: the band, or the per-pixel path's column weights
+  const int y0 = blockIdx.y * kRowsPerBlock;
+  const int rows = p.oh - y0 < kRowsPerBlock ? p.oh - y0 : kRowsPerBlock;
+  // grid.z covers the batch, strided where the batch is larger than a grid may be
+  for (long bl = blockIdx.z; bl < p.B; bl += gridDim.z) {
+    const int b = (int)bl;
+    // this block's image, or none: everything below is uniform over the block
+    long srci = p.index ? p.index[b] : bl;
+    long off = 0, H = 0, W = 0;
+    bool ok = srci >= 0 && srci < p.n_images;
+    if (ok) {
+      off = p.geom[srci * 3];
+      H = p.geom[srci * 3 + 1];
+      W = p.geom[srci * 3 + 2];
+      // H, W < 2^15, so 3 * H * W < 2^32 and the comparison cannot overflow
+      ok = H > 0 && H < (1 << 15) && W > 0 && W < (1 << 15) && off >= 0 && 3 * H * W <= p.n_bytes &&
+           off <= p.n_bytes - 3 * H * W;
+    }
+    if (threadIdx.x == 0 && threadIdx.y == 0 && blockIdx.x == 0 && blockIdx.y == 0 && p.labels_in && p.labels_out)
+      p.labels_out[b] = ok ? p.labels_in[srci] : -1;
+    if (!ok) {  // never read through: NaN for this output alone
+      const int xo = blockIdx.x * kColsPerBlock + threadIdx.x;
+      if (xo < p.ow) {
+        const long pl = (long)p.oh * p.ow;
+        float* o = p.out + (long)b * 3 * pl + xo;
+        for (int r = threadIdx.y; r < rows; r += kRowLanes)
+          for (int c = 0; c < 3; ++c) o[c * pl + (long)(y0 + r) * p.ow] = __builtin_nanf("");
+      }
+      continue;
+    }
+    const Axis ax = make_axis((int)W, p.ow), ay = make_axis((int)H, p.oh);
+    const int ksx = axis_ksize_dev(ax), ksy = axis_ksize_dev(ay);
+    const int ks = ksx > ksy ? ksx : ksy;
+    const uint8_t* img = p.bytes + off;
+    if (ks <= 3)
+      ragged_tiled<3>(p, img, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
+    else if (ks <= 5)
+      ragged_tiled<5>(p, img, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
+    else if (ks <= 9)
+      ragged_tiled<9>(p, img, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
+    else
+      ragged_pixel(p, img, ax, ay, ksx, b, y0, rows, s_h);
+    __syncthreads();  // the next image of this block reuses the LDS
+  }
+}
+
 }  // namespace
+
+extern "C" int vit_preprocess_u8_ragged(const uint8_t* bytes, int64_t n_bytes, const int64_t* geom, int64_t n_images,
+                                        const int64_t* index, int64_t B, const uint8_t* flips, int64_t out_h,
+                                        int64_t out_w, const float* mean_std, float* out, const int64_t* labels_in,
+                                        int64_t* labels_out, vit_stream_t stream) {
+  VIT_CHECK_ARG(bytes && geom && out && mean_std, "vit_preprocess_u8_ragged: null bytes / geom / out / mean_std");
+  VIT_CHECK_ARG(B > 0 && n_images > 0 && n_bytes > 0 && out_h > 0 && out_w > 0,
+                "vit_preprocess_u8_ragged: B, n_images, n_bytes and the output size must be positive");
+  VIT_CHECK_ARG(out_h < (1 << 15) && out_w < (1 << 15) && B < (1LL << 31) && B * out_h * out_w < (1LL << 40) &&
+                    n_images < (1LL << 40),
+                "vit_preprocess_u8_ragged: sizes too large");
+  RaggedArgs p;
+  p.bytes = bytes;
+  p.n_bytes = n_bytes;
+  p.geom = geom;
+  p.n_images = n_images;
+  p.index = index;
+  p.B = B;
+  p.flips = flips;
+  p.oh = (int)out_h;
+  p.ow = (int)out_w;
+  for (int c = 0; c < 3; ++c) {
+    p.mean[c] = mean_std[c];
+    p.stdv[c] = mean_std[3 + c];
+  }
+  p.out = out;
+  p.labels_in = labels_in;
+  p.labels_out = labels_out;
+  const long cb = (out_w + kColsPerBlock - 1) / kColsPerBlock, rb = (out_h + kRowsPerBlock - 1) / kRowsPerBlock;
+  // at most 65535 in z and fewer than 2^32 threads in the grid: the kernel strides the batch over z
+  const long z = std::max(1L, std::min({(long)B, 65535L, ((1L << 24) - 1) / (cb * rb)}));
+  hipLaunchKernelGGL(preprocess_ragged_kernel, dim3((unsigned)cb, (unsigned)rb, (unsigned)z),
+                     dim3(kColsPerBlock, kRowLanes), 0, (hipStream_t)stream, p);
+  VIT_LAUNCH_CHECK("vit_preprocess_u8_ragged");
+}
 
 extern "C" int vit_preprocess_u8(const uint8_t* images, int64_t B, int64_t H, int64_t W, int64_t image_stride,
                                  const uint8_t* flips, int64_t out_h, int64_t out_w, const float* mean_std,

@@ -17,16 +17,26 @@ src/config.py:57-104). Additions for the MI355X path, all optional:
 Without --synthetic, the reference's own commands run on CIFAR read from disk (vitmi.datasets, vitmi.data):
     python -m vitmi.train --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path w.pth ...
     python -m vitmi.eval  --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path ft.pth ...
-  --dataset CIFAR10 | CIFAR100 (ImageNet / TinyImageNet need JPEG decoding and are refused with that reason)
+  --dataset CIFAR10 | CIFAR100 | ImageNet | TinyImageNet
   --data-dir D           the files live under D/<dataset>/ as src/train.py:135 joins it, in either published form:
                            cifar-10-batches-py/{data_batch_1..5,test_batch}   cifar-100-python/{train,test}
                            cifar-10-batches-bin/{data_batch_1..5,test_batch}.bin   cifar-100-binary/{train,test}.bin
                          nothing is downloaded; a missing directory is an error naming the paths tried
-  --num-workers          accepted and unused: the set is resident in HBM and transformed there, one launch per batch
+  --num-workers          CIFAR: accepted and unused (the set is resident in HBM and transformed there, one launch per
+                         batch). Image folders: the threads that decode files, at most 16 (no worker processes)
   --seed                 seeds the sample order, which is the reference's DataLoader(shuffle=True,
                          generator=manual_seed(seed)) order epoch after epoch, and, through a second generator, the
                          flips. The flips follow the reference's rule (rand < 0.5 per sample) but not its draws: it
                          makes them inside its worker processes, whose streams depend on --num-workers
+ImageNet and TinyImageNet are image folders (vitmi.datasets.find_image_folder / find_tiny_imagenet): the files are
+decoded on the host with Pillow, as the reference's loader does, and resized on the device, whatever their sizes, by
+one launch per batch (vit_preprocess_u8_ragged), to the pair (h, w) of --image-size (the reference's Resize((s, s))):
+                           D/ImageNet/{train,val}/<class>/**/<image files>          (torchvision ImageFolder's rules)
+                           D/TinyImageNet/{train,val}/<class>/images/<files>, or the published val/images/ +
+                           val/val_annotations.txt
+  --resident-data        decode the whole split once and keep it in HBM (TinyImageNet's default); without it ImageNet
+                         streams: a thread decodes the next batches while the step runs
+  --resident-gb G        refuse a resident split larger than G GB (default 32)
   --n-gpu k              every rank takes its contiguous slice of each global batch (DataParallel's scatter); a ragged
                          last global batch is kept for k = 1, split when k divides it, otherwise skipped (one line
                          says how many images per epoch that leaves out)
@@ -53,6 +63,10 @@ def _add_common(parser, train: bool):
     parser.add_argument("--synthetic-source-size", type=int, default=0,
                         help="synthetic uint8 images of this size through the device transform (0: f32 N(0,1))")
     parser.add_argument("--any-image-size", default=False, action="store_true", help="allow any --image-size")
+    parser.add_argument("--resident-data", default=False, action="store_true",
+                        help="image folders: decode the split once and keep it in HBM instead of streaming it")
+    parser.add_argument("--resident-gb", type=float, default=32.0,
+                        help="image folders: the largest decoded split --resident-data may hold, in GB")
 
 
 def _image_size(text):
@@ -85,7 +99,7 @@ def get_eval_config(argv=None):
     parser.add_argument("--checkpoint-path", type=str, default=None, help="model checkpoint to load weights")
     _image_size_arg(parser, 384)
     parser.add_argument("--num-workers", type=int, default=8,
-                        help="accepted and unused (the dataset is resident in HBM: no host workers)")
+                        help="image folders: decode threads, at most 16; unused for CIFAR (resident in HBM)")
     parser.add_argument("--dataset", type=str, default="ImageNet", help="dataset for fine-tunning/evaluation")
     parser.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"],
                         help="bf16 MFMA forward or the reference's f32 arithmetic")
@@ -107,7 +121,7 @@ def get_train_config(argv=None):
                         help="model checkpoint to load weights")
     _image_size_arg(parser, 224)
     parser.add_argument("--num-workers", type=int, default=1,
-                        help="accepted and unused (the dataset is resident in HBM: no host workers)")
+                        help="image folders: decode threads, at most 16; unused for CIFAR (resident in HBM)")
     parser.add_argument("--train-steps", type=int, default=15000, help="number of training/fine-tunning steps")
     parser.add_argument("--lr", type=float, default=0.03, help="learning rate")
     parser.add_argument("--wd", type=float, default=0.0, help="weight decay")

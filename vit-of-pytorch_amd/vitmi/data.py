@@ -9,9 +9,11 @@ torchvision's PIL path; oracle/preprocess.py, tests/test_preprocess_cpu.py and
 tests/test_preprocess_gpu.py). Flip draws come from a torch.Generator: the per-worker RNG streams
 of the reference's DataLoader are not reproducible, the decision rule (rand < p) is the same.
 
-Real datasets (vitmi.datasets: CIFAR-10/100 parsed from disk) go through ResidentLoader: the set stays
+Real datasets (vitmi.datasets): CIFAR-10/100 parsed from disk go through ResidentLoader: the set stays
 in HBM as stored (planar uint8), the sample order is the reference's seeded DataLoader order
-(epoch_order), and each step's batch is one vit_preprocess_u8_gather launch.
+(epoch_order), and each step's batch is one vit_preprocess_u8_gather launch. ImageNet / TinyImageNet image
+folders go through FolderLoader: files decoded on the host by Pillow, of whatever sizes, packed end to end, and
+each step's batch is one vit_preprocess_u8_ragged launch, streamed or resident. `loaders` picks by --dataset.
 """
 from __future__ import annotations
 
@@ -164,9 +166,8 @@ def cifar_loaders(config, batch_size, device, world=1, rank=0, splits=("train", 
     (the reference's split='val') in file order. `batch_size` is the per-rank batch."""
     from . import datasets
     if config.dataset not in datasets.SUPPORTED:
-        raise SystemExit(f"--dataset {config.dataset} is not supported without --synthetic: this path reads "
-                         f"{' and '.join(datasets.SUPPORTED)} from --data-dir (ImageNet / TinyImageNet need JPEG "
-                         "decoding, which is outside it)")
+        raise SystemExit(f"--dataset {config.dataset} is not supported without --synthetic: this project reads "
+                         f"{ON_DISK_FORMS}")
     root = os.path.join(config.data_dir, config.dataset)
     loaders = []
     for split in splits:
@@ -178,6 +179,271 @@ def cifar_loaders(config, batch_size, device, world=1, rank=0, splits=("train", 
         except (datasets.DatasetError, ValueError) as e:
             raise SystemExit(f"{config.dataset} {split} split: {e}") from e
     return loaders
+
+
+class _Slot:
+    """one batch in flight from the producer to the launch that reads it: a pinned host buffer and its device
+    copy for the packed bytes and for the table (geometry rows, then labels)"""
+
+    def __init__(self, batch_size, device):
+        self.device = device
+        self.host_meta = torch.empty(batch_size * 4, dtype=torch.int64).pin_memory()
+        self.dev_meta = torch.empty(batch_size * 4, dtype=torch.int64, device=device)
+        self.host_bytes = self.dev_bytes = None
+        self.copied = torch.cuda.Event()  # the upload of this slot's batch, on the side stream
+        self.consumed = None  # recorded by the consumer behind the launch that read the slot
+
+    def reserve(self, n_bytes):
+        if self.host_bytes is None or self.host_bytes.numel() < n_bytes:
+            cap = n_bytes + n_bytes // 4
+            self.host_bytes = torch.empty(cap, dtype=torch.uint8).pin_memory()
+            self.dev_bytes = torch.empty(cap, dtype=torch.uint8, device=self.device)
+
+
+def _checked_image(a, path):
+    """a decoded image as the device transform takes it: uint8 [H, W, 3], 0 < H, W < 2^15, contiguous"""
+    import numpy as np
+    from .datasets import DatasetError
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise DatasetError(f"{path}: decoded to {a.dtype} {a.shape}, expected uint8 [H, W, 3]")
+    if not (0 < a.shape[0] < 1 << 15 and 0 < a.shape[1] < 1 << 15):
+        raise DatasetError(f"{path}: {a.shape[0]} x {a.shape[1]} pixels; the device transform takes sides in "
+                           "[1, 32767]")
+    return np.ascontiguousarray(a)
+
+
+class FolderLoader:
+    """Image files of any sizes (ImageNet / TinyImageNet folders), decoded on the host and transformed on the
+    device by one launch per batch.
+
+    The reference feeds its step from `DataLoader(ImageFolder(transform=Resize((s, s)) -> RandomHorizontalFlip ->
+    ToTensor -> Normalize), shuffle=train, generator=manual_seed(seed), num_workers=k)` (src/data_loaders.py:96-124,
+    res-vit/data_loaders.py:96-216). Here EpochPlan gives the same sample order, the flip rule, the ranks' slices
+    and the ragged last batch, `decode` (datasets.decode_rgb: Pillow, as the reference) turns a path into uint8
+    [H, W, 3], and vit_preprocess_u8_ragged resizes every image of a batch from its own size to `image_size`
+    (always the pair (h, w)), flips, normalises and picks the labels in one launch, bit-exact to Pillow's resize.
+
+    streaming (resident=False)  a producer thread decodes the coming batches on a pool of min(workers, 16) threads
+        (Pillow releases the GIL while it decodes; no worker processes), packs each batch end to end into a pinned
+        buffer with its (offset, H, W) table and labels and uploads both on a side stream. `depth` slots go round;
+        events order the upload before the launch that reads a slot, and that launch before the slot's next
+        overwrite. The consuming loop only waits for the producer's queue: it never synchronises the device.
+    resident=True  one decode pass packs the whole split into HBM with its table and labels (refused above
+        `resident_gb`); then a batch is one launch with index = order[s:e], with no host work per step.
+
+    `data_wait_s` is the time the last (or running) epoch's consumer spent waiting for the producer.
+    `batch_size` is this rank's batch. Yields (float32 [b, 3, h, w], int64 [b]) on the device."""
+
+    def __init__(self, paths, labels, batch_size, image_size, device, train=True, seed=42, world=1, rank=0,
+                 num_classes=None, workers=8, resident=False, resident_gb=32.0, decode=None, depth=2,
+                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)):
+        from . import datasets
+        self.paths = list(paths)
+        labels = torch.as_tensor(labels).reshape(-1)
+        if labels.numel() != len(self.paths):
+            raise ValueError(f"FolderLoader: {len(self.paths)} paths but {labels.numel()} labels")
+        labels = check_labels(labels, num_classes) if num_classes is not None else labels.to(torch.int64).cpu()
+        self.host_labels = labels.contiguous()
+        self.plan = EpochPlan(len(self.paths), batch_size, train, seed, world, rank)
+        if self.plan.skipped and rank == 0:
+            print(f"{'train' if train else 'eval'} loader: the last {self.plan.skipped} images of each epoch's order "
+                  f"do not divide over {world} ranks and are left out (every epoch)", flush=True)
+        self.out_hw = (int(image_size), int(image_size)) if isinstance(image_size, int) else \
+            (int(image_size[0]), int(image_size[1]))
+        self.mean, self.std = tuple(mean), tuple(std)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:  # the producer thread names it by index
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.decode = datasets.decode_rgb if decode is None else decode
+        self.workers = max(1, min(int(workers), 16))  # never the machine's CPU count
+        self.depth = max(2, int(depth))
+        self.resident = bool(resident)
+        self.data_wait_s = 0.0
+        self.last_flips = None
+        self.order = self.flips = None
+        if self.resident:
+            self._load_resident(resident_gb)
+
+    def __len__(self):
+        return len(self.plan)
+
+    # -- resident ------------------------------------------------------------------------------------------
+    def _load_resident(self, resident_gb):
+        import numpy as np
+        from concurrent.futures import ThreadPoolExecutor
+        from .datasets import DatasetError
+        limit = int(float(resident_gb) * (1 << 30))
+        n = len(self.paths)
+        geom = np.zeros((n, 3), np.int64)
+        chunks, total = [], 0
+        with ThreadPoolExecutor(self.workers, thread_name_prefix="vitmi-decode") as pool:
+            for s in range(0, n, 256):
+                part = [_checked_image(a, p) for a, p in
+                        zip(pool.map(self.decode, self.paths[s:s + 256]), self.paths[s:s + 256])]
+                for i, a in enumerate(part):
+                    geom[s + i] = (total, a.shape[0], a.shape[1])
+                    total += a.size
+                if total > limit:
+                    raise DatasetError(f"the decoded split passes --resident-gb {resident_gb:g} after {s + len(part)} "
+                                       f"of {n} images ({total / (1 << 30):.1f} GB): drop --resident-data to stream "
+                                       "it, or raise --resident-gb")
+                chunks.append(np.concatenate([a.reshape(-1) for a in part]))
+        self.bytes = torch.empty(total, dtype=torch.uint8, device=self.device)
+        pos = 0
+        for c in chunks:
+            self.bytes[pos:pos + c.size].copy_(torch.from_numpy(c))
+            pos += c.size
+        self.geom = torch.from_numpy(geom).to(self.device)
+        self.labels = self.host_labels.to(self.device)
+
+    def _iter_resident(self):
+        h, w = self.out_hw
+        for s, e in self.plan.slices():
+            out = torch.empty(e - s, 3, h, w, device=self.device, dtype=torch.float32)
+            target = torch.empty(e - s, device=self.device, dtype=torch.int64)
+            ops.preprocess_u8_ragged(self.bytes, self.geom, out, index=self.order[s:e],
+                                     flips=None if self.flips is None else self.flips[s:e], mean=self.mean,
+                                     std=self.std, labels_in=self.labels, labels_out=target)
+            yield out, target
+
+    # -- streaming -----------------------------------------------------------------------------------------
+    def _produce(self, order, slices, pool, free, ready, stop, stream):
+        """the producer thread: decode ahead, pack, upload; hands (slot, count, bytes) or an exception to `ready`"""
+        from collections import deque
+        try:
+            torch.cuda.set_device(self.device)
+            pending, nxt = deque(), 0
+            for _ in slices:
+                while nxt < len(slices) and len(pending) <= self.depth:  # decode up to depth batches ahead
+                    s, e = slices[nxt]
+                    idx = order[s:e].tolist()
+                    pending.append((idx, [pool.submit(self.decode, self.paths[i]) for i in idx]))
+                    nxt += 1
+                idx, futures = pending.popleft()
+                images = [_checked_image(f.result(), self.paths[i]) for f, i in zip(futures, idx)]
+                slot = free.get()
+                if slot is None or stop.is_set():
+                    return
+                if slot.consumed is not None:
+                    slot.consumed.synchronize()  # the launch that read this slot last has run
+                b, n_bytes = len(images), sum(a.size for a in images)
+                slot.reserve(n_bytes)
+                host, meta, pos = slot.host_bytes.numpy(), slot.host_meta.numpy(), 0
+                for k, a in enumerate(images):
+                    host[pos:pos + a.size] = a.reshape(-1)
+                    meta[3 * k:3 * k + 3] = (pos, a.shape[0], a.shape[1])
+                    pos += a.size
+                meta[3 * b:4 * b] = self.host_labels[idx].numpy()
+                with torch.cuda.stream(stream):
+                    slot.dev_bytes[:n_bytes].copy_(slot.host_bytes[:n_bytes], non_blocking=True)
+                    slot.dev_meta[:4 * b].copy_(slot.host_meta[:4 * b], non_blocking=True)
+                    slot.copied.record(stream)
+                ready.put((slot, b, n_bytes))
+        except BaseException as e:  # surfaces in the consuming loop
+            ready.put(e)
+
+    def _iter_streaming(self, order):
+        import queue
+        import threading
+        import time
+        from concurrent.futures import ThreadPoolExecutor
+        h, w = self.out_hw
+        slices = self.plan.slices()
+        bmax = max(e - s for s, e in slices)
+        free, ready, stop = queue.Queue(), queue.Queue(), threading.Event()
+        for _ in range(self.depth):
+            free.put(_Slot(bmax, self.device))
+        pool = ThreadPoolExecutor(self.workers, thread_name_prefix="vitmi-decode")
+        stream = torch.cuda.Stream(self.device)
+        producer = threading.Thread(target=self._produce, args=(order, slices, pool, free, ready, stop, stream),
+                                    name="vitmi-producer", daemon=True)
+        producer.start()
+        try:
+            for s, e in slices:
+                t0 = time.perf_counter()
+                item = ready.get()
+                self.data_wait_s += time.perf_counter() - t0
+                if isinstance(item, BaseException):
+                    raise item
+                slot, b, n_bytes = item
+                out = torch.empty(b, 3, h, w, device=self.device, dtype=torch.float32)
+                target = torch.empty(b, device=self.device, dtype=torch.int64)
+                cur = torch.cuda.current_stream(self.device)
+                cur.wait_event(slot.copied)
+                ops.preprocess_u8_ragged(slot.dev_bytes, slot.dev_meta[:3 * b].view(b, 3), out,
+                                         flips=None if self.flips is None else self.flips[s:e], mean=self.mean,
+                                         std=self.std, labels_in=slot.dev_meta[3 * b:4 * b], labels_out=target,
+                                         n_bytes=n_bytes)
+                slot.dev_bytes.record_stream(cur)
+                slot.dev_meta.record_stream(cur)
+                slot.consumed = torch.cuda.Event()
+                slot.consumed.record(cur)
+                free.put(slot)
+                yield out, target
+        finally:
+            stop.set()
+            free.put(None)
+            pool.shutdown(wait=True, cancel_futures=True)
+            producer.join()
+
+    def __iter__(self):
+        if self.order is None or self.plan.train:
+            order, flips = self.plan.next_epoch()
+            self.last_flips = flips
+            self.host_order = order
+            self.order = order.to(self.device)
+            self.flips = None if flips is None else flips.to(self.device)
+        self.data_wait_s = 0.0
+        return self._iter_resident() if self.resident else self._iter_streaming(self.host_order)
+
+
+FOLDER_DATASETS = ("ImageNet", "TinyImageNet")
+ON_DISK_FORMS = (
+    "CIFAR10 and CIFAR100 in their published python or binary form (<data-dir>/CIFAR10/cifar-10-batches-py or "
+    "cifar-10-batches-bin, <data-dir>/CIFAR100/cifar-100-python or cifar-100-binary); ImageNet as image folders "
+    "(<data-dir>/ImageNet/train/<class>/<image files> and <data-dir>/ImageNet/val/<class>/<image files>); "
+    "TinyImageNet as <data-dir>/TinyImageNet/train/<class>/images/<image files> with val/ in the same form or as "
+    "the published val/images/ + val/val_annotations.txt")
+
+
+def folder_loaders(config, batch_size, device, world=1, rank=0, splits=("train", "test")):
+    """The reference's ImageNetDataLoader / TinyImageNetDataLoader pair (src/train.py:134-147 with
+    src/data_loaders.py:96-124, res-vit/data_loaders.py:96-216) as FolderLoaders over
+    <data-dir>/<dataset>/{train,val}: 'train' shuffled and flipped, 'test' (the reference's split='val') in file
+    order. ImageNet streams unless --resident-data; TinyImageNet is resident. --num-workers sizes the decode pool."""
+    from . import datasets
+    root = os.path.join(config.data_dir, config.dataset)
+    resident = bool(getattr(config, "resident_data", False)) or config.dataset == "TinyImageNet"
+    loaders_ = []
+    for split in splits:
+        sub = "train" if split == "train" else "val"
+        try:
+            if not os.path.isdir(os.path.join(root, sub)):
+                raise datasets.DatasetError(f"looked for the directory {os.path.join(root, sub)} and did not find it "
+                                            f"(nothing is downloaded or created here). This project reads: "
+                                            f"{ON_DISK_FORMS}")
+            if config.dataset == "ImageNet":
+                paths, labels, _ = datasets.find_image_folder(os.path.join(root, sub))
+            else:
+                paths, labels, _ = datasets.find_tiny_imagenet(root, sub)
+            from .config import image_hw
+            loaders_.append(FolderLoader(paths, labels, batch_size, image_hw(config.image_size), device,
+                                         train=split == "train", seed=config.seed, world=world, rank=rank,
+                                         num_classes=config.num_classes, workers=getattr(config, "num_workers", 8),
+                                         resident=resident, resident_gb=getattr(config, "resident_gb", 32.0)))
+        except (datasets.DatasetError, ValueError) as e:
+            raise SystemExit(f"{config.dataset} {sub} split: {e}") from e
+    return loaders_
+
+
+def loaders(config, batch_size, device, world=1, rank=0, splits=("train", "test")):
+    """The loaders of `--dataset`, one per split ('train', 'test' = the evaluation split): CIFAR10 / CIFAR100 as
+    ResidentLoaders (cifar_loaders), ImageNet / TinyImageNet as FolderLoaders (folder_loaders). Any other name
+    exits with the list of what is read."""
+    if config.dataset in FOLDER_DATASETS:
+        return folder_loaders(config, batch_size, device, world, rank, splits)
+    return cifar_loaders(config, batch_size, device, world, rank, splits)
 
 
 class GPUTransform:

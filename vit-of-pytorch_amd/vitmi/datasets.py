@@ -1,4 +1,5 @@
-"""CIFAR-10 / CIFAR-100 from disk, without torchvision (host only: no GPU, no library).
+"""CIFAR-10 / CIFAR-100 and ImageNet / TinyImageNet image folders from disk, without torchvision (host only:
+no GPU, no library). CIFAR first; the image folders are at the end of this file.
 
 The reference builds its loaders from `torchvision.datasets.CIFAR10 / CIFAR100(root=os.path.join(
 config.data_dir, config.dataset), download=True)` (src/train.py:134-147, src/data_loaders.py:50,82).
@@ -169,3 +170,122 @@ def load_cifar(root, name, train=True):
     if labels.size and (labels.min() < 0 or labels.max() >= spec["classes"]):
         raise DatasetError(f"{name}: labels span [{labels.min()}, {labels.max()}], expected [0, {spec['classes']})")
     return images, labels, _class_names(spec, base, form)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Image folders: ImageNet (src/data_loaders.py:96-124, res-vit/data_loaders.py:188-216: torchvision's
+# ImageFolder over <data-dir>/ImageNet/{train,val}) and TinyImageNet (res-vit/data_loaders.py:96-185: its own
+# walk over <class>/images/). Only the file lists are made here; decoding is decode_rgb, one file at a time, and
+# the resize happens on the device (vit_preprocess_u8_ragged), so images keep the sizes they have on disk.
+
+IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
+TINY_EXTENSIONS = (".png", ".jpg", ".jpeg")
+
+
+def _class_dirs(root, what):
+    if not os.path.isdir(root):
+        raise DatasetError(f"{what} not found: looked for the directory {root} (nothing is downloaded or created "
+                           "here)")
+    with os.scandir(root) as it:
+        return sorted(e.name for e in it if e.is_dir())
+
+
+def find_image_folder(root):
+    """(paths [n], labels int64 [n], classes) of the images under `root`, one sub-directory per class, under
+    the rules of torchvision's `ImageFolder` (`datasets.folder.find_classes` / `make_dataset`). torchvision is
+    not importable here, so the rules are restated, not called: the classes are the sorted names of the
+    directories directly under root, class i gets label i; per class, in class order, the directory is walked
+    with `sorted(os.walk(dir, followlinks=True))` and within each directory the sorted file names are taken;
+    a file is kept when its lower-cased extension is one of IMG_EXTENSIONS. A class directory without any image
+    is an error, as it is in torchvision, and so is a root without class directories."""
+    classes = _class_dirs(root, "image folder")
+    if not classes:
+        raise DatasetError(f"{root} holds no class directories (expected {root}/<class>/<image files>)")
+    paths, labels, empty = [], [], []
+    for idx, cls in enumerate(classes):
+        before = len(paths)
+        for d, _, names in sorted(os.walk(os.path.join(root, cls), followlinks=True)):
+            for fn in sorted(names):
+                if fn.lower().endswith(IMG_EXTENSIONS):
+                    paths.append(os.path.join(d, fn))
+                    labels.append(idx)
+        if len(paths) == before:
+            empty.append(cls)
+    if empty:
+        raise DatasetError(f"{root}: found no image file for the class{'es' if len(empty) > 1 else ''} "
+                           f"{', '.join(empty[:5])}{' ...' if len(empty) > 5 else ''} (extensions "
+                           f"{', '.join(IMG_EXTENSIONS)})")
+    return paths, np.asarray(labels, np.int64), classes
+
+
+def find_tiny_imagenet(root, split):
+    """(paths, labels int64, classes) of the `split` ('train', 'val' or 'test') of TinyImageNet under `root`,
+    as res-vit/data_loaders.py:124-152 lists it: the classes are `sorted(os.listdir(root/split))`, class i gets
+    label i, and the samples of a class are the .png / .jpg / .jpeg files of `<class>/images/`. The reference
+    takes them in `os.listdir` order, which depends on the file system and cannot be reproduced by anyone; here
+    they are taken in sorted order, so the list is the same on every machine (the evaluation result does not
+    depend on the order, the shuffled training order does).
+    The published download stores its validation split differently: `val/images/*.JPEG` plus
+    `val/val_annotations.txt` (file name, class id, box). On that form the reference's walk finds the single
+    'class' images with no samples; here it is read: the label of a file is the position of its class id among
+    the sorted class ids of `root/train`, the files are taken in sorted order."""
+    base = os.path.join(root, split)
+    annotations = os.path.join(base, "val_annotations.txt")
+    if os.path.isfile(annotations) and os.path.isdir(os.path.join(base, "images")):
+        classes = _class_dirs(os.path.join(root, "train"), "TinyImageNet train split (its class ids label the "
+                              "annotated validation files)")
+        index = {c: i for i, c in enumerate(classes)}
+        wnid = {}
+        with open(annotations, "r", encoding="utf-8") as f:
+            for line in f:
+                parts = line.split()
+                if len(parts) >= 2:
+                    wnid[parts[0]] = parts[1]
+        paths, labels = [], []
+        for fn in sorted(os.listdir(os.path.join(base, "images"))):
+            if not fn.lower().endswith(TINY_EXTENSIONS):
+                continue
+            if fn not in wnid:
+                raise DatasetError(f"{annotations} has no line for {fn}")
+            if wnid[fn] not in index:
+                raise DatasetError(f"{annotations}: {fn} is labelled {wnid[fn]}, which is no directory of "
+                                   f"{os.path.join(root, 'train')}")
+            paths.append(os.path.join(base, "images", fn))
+            labels.append(index[wnid[fn]])
+    else:
+        if not os.path.isdir(base):
+            raise DatasetError(f"TinyImageNet {split} split not found: looked for the directory {base} (nothing "
+                               "is downloaded or created here)")
+        classes = sorted(os.listdir(base))
+        paths, labels = [], []
+        for idx, cls in enumerate(classes):
+            d = os.path.join(base, cls, "images")
+            if os.path.isdir(d):
+                for fn in sorted(os.listdir(d)):
+                    if fn.lower().endswith(TINY_EXTENSIONS):
+                        paths.append(os.path.join(d, fn))
+                        labels.append(idx)
+    if not paths:
+        raise DatasetError(f"{base} holds no image: expected <class>/images/*.JPEG, or images/ with "
+                           "val_annotations.txt")
+    return paths, np.asarray(labels, np.int64), classes
+
+
+def decode_rgb(path):
+    """The reference's loader, `PIL.Image.open(path).convert('RGB')` (torchvision's `pil_loader`,
+    res-vit/data_loaders.py:169), as uint8 [H, W, 3]: grayscale, palette, RGBA and CMYK files become RGB by
+    Pillow's own rules. Pillow is the decoder and is imported here, not with the module, so everything else in
+    this file works without it."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise DatasetError(f"decoding image files needs Pillow (PIL), which is not importable here: {e}") from e
+    try:
+        with open(path, "rb") as f:
+            with Image.open(f) as im:
+                a = np.asarray(im.convert("RGB"), dtype=np.uint8)
+    except Exception as e:  # a truncated or foreign file, or one that is not there
+        raise DatasetError(f"{path}: cannot be decoded as an image ({type(e).__name__}: {e})") from e
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise DatasetError(f"{path}: decoded to shape {a.shape}, expected [H, W, 3]")
+    return np.ascontiguousarray(a)

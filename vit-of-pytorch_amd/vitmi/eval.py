@@ -11,10 +11,15 @@ B/16 and L/16, 730 for H/14) run the K/V-tiled attention kernels. `--precision f
 the reference's own f32 arithmetic (vit_gemm_f32 projections, f32 attention).
 Data: `--dataset CIFAR10|CIFAR100 --data-dir D` evaluates the test split read from disk and kept in HBM
 (vitmi.datasets, vitmi.data.ResidentLoader), in file order; `--synthetic` a synthetic split, as in
-vitmi.train. ImageNet (the default --dataset) needs JPEG decoding and is not supported.
+vitmi.train. `--dataset ImageNet` (the default) evaluates the image folder D/ImageNet/val/<class>/..., and
+`--dataset TinyImageNet` D/TinyImageNet/val in either of its forms (vitmi.datasets), in file order: the files are
+decoded on the host with Pillow, --num-workers threads at a time, while the device works on the batch before, and
+every image, whatever its size, is resized to --image-size on the device (vitmi.data.FolderLoader).
 
     python -m vitmi.eval --model-arch b16 --image-size 224 --dataset CIFAR100 --num-classes 100 \\
         --data-dir ../data --checkpoint-path ft.pth
+    python -m vitmi.eval --model-arch b16 --image-size 384 --dataset ImageNet --data-dir ../data \\
+        --checkpoint-path ../weights/pytorch/imagenet21k+imagenet2012_ViT-B_16-384.pth
 """
 from __future__ import annotations
 
@@ -54,8 +59,8 @@ def main(argv=None):
     if not config.synthetic:
         # the reference's {dataset}DataLoader(split='val') (src/eval.py:44-50): the test split, in file order; read
         # before the model is built, so that a missing dataset stops the run at once
-        from .data import cifar_loaders
-        data_loader, = cifar_loaders(config, config.batch_size, device, splits=("test",))
+        from .data import loaders
+        data_loader, = loaders(config, config.batch_size, device, splits=("test",))
     model = build_model(config, device)
     if config.checkpoint_path:
         state_dict = fit_pos_embedding(load_checkpoint(config.checkpoint_path), model, config)

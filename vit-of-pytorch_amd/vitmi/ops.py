@@ -272,6 +272,44 @@ def preprocess_u8_gather(images, index, out, flips=None, mean=(0.5, 0.5, 0.5), s
                                          _stream()), "vit_preprocess_u8_gather")
 
 
+def preprocess_u8_ragged(bytes, geom, out, index=None, flips=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5),
+                         labels_in=None, labels_out=None, n_bytes=None):
+    """out[b] = preprocess_u8's transform of source image index[b] (index None: image b), the images of one
+    batch differing in size, in one launch (vit_preprocess_u8_ragged).
+    bytes: uint8, 1-D on the device: the images end to end, each HWC; geom int64 [n, 3] on the device, row i =
+    (offset, H, W) of image i; `n_bytes` (default bytes.numel()) is how much of `bytes` a table row may reach.
+    index int64 [B], flips uint8 [B] (by output image), out f32 [B, 3, h, w]; labels_out[b] = labels_in[index[b]]
+    when both are given (int64 [n] / [B]). A bad index or a table row that does not fit `n_bytes` gives a NaN
+    image and label -1 for that output alone; the library refuses null pointers and empty or oversized batches."""
+    _chk(bytes, torch.uint8, "bytes")
+    _chk(geom, torch.int64, "geom")
+    _chk(out, F32, "out")
+    _chk(index, torch.int64, "index")
+    _chk(flips, torch.uint8, "flips")
+    _chk(labels_in, torch.int64, "labels_in")
+    _chk(labels_out, torch.int64, "labels_out")
+    if bytes.dim() != 1 or geom.dim() != 2 or geom.shape[1] != 3 or out.dim() != 4 or out.shape[1] != 3:
+        raise ValueError(f"preprocess_u8_ragged: bytes [n_bytes], geom [n,3] -> out [B,3,h,w], got "
+                         f"{tuple(bytes.shape)}, {tuple(geom.shape)} -> {tuple(out.shape)}")
+    n, B = geom.shape[0], out.shape[0]
+    if (index is not None and (index.dim() != 1 or index.numel() != B)) or (index is None and B > n) or \
+            (flips is not None and flips.numel() != B) or (labels_out is not None and labels_out.numel() != B) or \
+            (labels_in is not None and labels_in.numel() != n):
+        raise ValueError("preprocess_u8_ragged: batch mismatch")
+    for name, t in (("bytes", bytes), ("geom", geom), ("out", out), ("index", index), ("flips", flips),
+                    ("labels_in", labels_in), ("labels_out", labels_out)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"preprocess_u8_ragged: {name} must be contiguous")
+    if n_bytes is None:
+        n_bytes = bytes.numel()
+    if not 0 <= int(n_bytes) <= bytes.numel():
+        raise ValueError(f"preprocess_u8_ragged: n_bytes {n_bytes} outside [0, {bytes.numel()}]")
+    ms = (ctypes.c_float * 6)(*[float(v) for v in mean], *[float(v) for v in std])
+    check(lib().vit_preprocess_u8_ragged(_p(bytes), int(n_bytes), _p(geom), n, _p(index), B, _p(flips), out.shape[2],
+                                         out.shape[3], ms, _p(out), _p(labels_in), _p(labels_out), _stream()),
+          "vit_preprocess_u8_ragged")
+
+
 def embed_grad(dh0, B, N, D, dpos, dcls, dconv_bias, dropout=None):
     check(lib().vit_embed_grad(_p(dh0), B, N, D, _p(dpos), _p(dcls), _p(dconv_bias), _dp(dropout), _stream()),
           "vit_embed_grad")

@@ -277,7 +277,7 @@ def get_train_config(argv=None):
     a("--image-size", type=_image_size, default=224, help="224 or 384; any int, or HxW, with --any-image-size")
     a("--any-image-size", default=False, action="store_true", help="allow any --image-size")
     a("--num-workers", type=int, default=1,
-      help="accepted and unused (the dataset is resident in HBM: no host workers)")
+      help="image folders: decode threads, at most 16; unused for CIFAR (resident in HBM)")
     a("--data-dir", type=str, default="../data/")
     a("--dataset", type=str, default="CIFAR100", choices=["CIFAR10", "CIFAR100", "ImageNet", "TinyImageNet"])
     a("--patch-size", type=int, default=16)
@@ -317,6 +317,10 @@ def get_train_config(argv=None):
     a("--no-save", default=False, action="store_true")
     a("--n-gpu", type=int, default=1, help="data-parallel ranks (one per GPU)")
     a("--fused-clip", default=False, action="store_true", help="fold clip_grad_norm_ into the AdamW update")
+    a("--resident-data", default=False, action="store_true",
+      help="image folders: decode the split once and keep it in HBM instead of streaming it")
+    a("--resident-gb", type=float, default=32.0,
+      help="image folders: the largest decoded split --resident-data may hold, in GB")
     config = p.parse_args(argv)
     _check_image_size(config)
     config.num_classes = get_num_classes_for_dataset(config.dataset)
@@ -369,8 +373,8 @@ def main(argv=None):
     train_loader = valid_loader = None
     if not config.synthetic:
         # res-vit/data_loaders.py:32-93 (the ViT driver's CIFAR loaders and transform): read from disk, resident in HBM
-        from .data import cifar_loaders
-        train_loader, valid_loader = cifar_loaders(config, batch, device, world, rank)
+        from .data import loaders
+        train_loader, valid_loader = loaders(config, batch, device, world, rank)
     optimizer = AdamW(model.parameters(), lr=config.lr, weight_decay=config.wd, betas=(config.beta1, config.beta2),
                       eps=config.eps, max_grad_norm=1.0 if (config.fused_clip and config.clip_grad_norm) else None)
     reducer = None
@@ -406,6 +410,8 @@ def main(argv=None):
                                 lr_scheduler if config.lr_scheduler == "cosine_with_warmup" else None, la, ld, lc,
                                 device, reducer=reducer)
         log.update(res)
+        if getattr(train_loader, "data_wait_s", None) is not None:
+            log["data_wait_s"] = round(train_loader.data_wait_s, 3)  # vitmi.data.FolderLoader: the host's share
         if config.lr_scheduler == "cosine":
             lr_scheduler.step()
         model.eval()

@@ -238,6 +238,10 @@ def train_epoch(epoch, model, data_loader, criterion, optimizer, lr_scheduler, m
             if not dist.is_initialized() or dist.get_rank() == 0:
                 print("Train Epoch: {:03d} Batch: {:05d}/{:05d} Loss: {:.4f} Acc@1: {:.2f}, Acc@5: {:.2f}"
                       .format(epoch, batch_idx, len(data_loader), *shown), flush=True)
+    wait = getattr(data_loader, "data_wait_s", None)
+    if wait is not None and (not dist.is_initialized() or dist.get_rank() == 0):
+        # vitmi.data.FolderLoader: how long this epoch's steps waited for decoded files (the host's share)
+        print("Train Epoch: {:03d} data_wait_s: {:.3f}".format(epoch, wait), flush=True)
     return metrics.result()
 
 
@@ -363,8 +367,8 @@ def main(argv=None):
     if not config.synthetic:
         # the reference's {dataset}DataLoader pair (src/train.py:134-147), read from disk and kept in HBM; before the
         # model, so that a missing dataset stops the run before a checkpoint is loaded
-        from .data import cifar_loaders
-        train_loader, valid_loader = cifar_loaders(config, batch, device, world, rank)
+        from .data import loaders
+        train_loader, valid_loader = loaders(config, batch, device, world, rank)
 
     model = build_model(config, device)
     if config.checkpoint_path:
