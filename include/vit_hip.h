@@ -151,6 +151,10 @@ int vit_gemm_splitk_group(const vit_gemm_args* args, int32_t n, vit_stream_t str
  * own K, split_k and batch. A member i with direct[i] != 0 (split_k must be 1) writes no slab: it stores the f32
  * result itself, C[z*c_batch_stride + m*ldc + n] = acc for m < M, n < N and nothing else, one accumulation chain
  * over all of K, bit-identical to the member's slab at split_k 1 reduced by vit_splitk_reduce. direct may be NULL.
+ * (ABI 23) direct[i] == 2: direct and accumulating, C[...] = C[...] + acc, one f32 add of the finished sum (what
+ * vit_splitk_reduce with accumulate gives at split_k 1, bit for bit); the same argument checks as direct[i] == 1.
+ * Each element belongs to one workgroup, so the result is deterministic. A table with such a member runs on a
+ * launch variant of its own; its other members behave as in any table. Values other than 0, 1, 2 are refused.
  *   vit_gemm_group_table_bytes(n): size of the table (0 for an n outside 1..VIT_GEMM_TABLE_MAX);
  *   vit_gemm_group_prepare: validates the members and uploads the table (16-byte aligned device memory the caller
  *     keeps alive); synchronises `stream` first, so a table may be rebuilt in place. Call it when the member list
@@ -341,6 +345,10 @@ int vit_preprocess_u8_ragged(const uint8_t* bytes, int64_t n_bytes, const int64_
  * dropout (optional): dh0 is taken through the position-embedding dropout's multipliers first. */
 int vit_embed_grad(const float* dh0, int64_t B, int64_t N, int64_t D, float* dpos, float* dcls,
                    float* dconv_bias, const vit_dropout* dropout, vit_stream_t stream);
+/* (ABI 23) the same with accumulate != 0: dpos, dcls and dconv_bias each become old + s, s being exactly the value
+ * vit_embed_grad writes, added once (gradient accumulation over micro-batches). accumulate == 0 is vit_embed_grad. */
+int vit_embed_grad_accum(const float* dh0, int64_t B, int64_t N, int64_t D, float* dpos, float* dcls,
+                         float* dconv_bias, const vit_dropout* dropout, int32_t accumulate, vit_stream_t stream);
 
 /* column sums: out[n] (+)= sum_r in[r*ld + n], in bf16 (in_bf16=1) or f32. `partial` needs
  * vit_colsum_partial_rows(rows) * cols floats. (bias grads, src/train.py:23 autograd) */

@@ -152,6 +152,70 @@ __global__ void __launch_bounds__(256) cls_bias_grad16_kernel(const float* __res
   }
 }
 
+// The accumulating embedding gradient (vit_embed_grad_accum): dpos, dcls and dconv_bias each become old + s, with s
+// the value vit_embed_grad writes, added once at the end. cls_bias_grad16_kernel reads dpos, which here holds the
+// accumulated table and no longer this micro-batch's sums, and there is no buffer to keep those in. So the three
+// kernels are restructured into one: a workgroup owns 16 columns (as cls_bias_grad16_kernel does) and walks every
+// token row; it re-forms each position sum s[n][d] from dh0 in the order of the position-gradient kernel the
+// overwriting call would pick (GROUPED: pos_grad4_kernel's 8 image groups, partial 0 first and the others added
+// in turn; otherwise pos_grad_kernel's single chain over the images), adds it into dpos, and feeds the same value into
+// the bias sums in cls_bias_grad16_kernel's order: 16 row lanes, lane R the rows 1 + R, 17 + R, ... ascending, then
+// lanes 0..15 in turn. Threads: 16 columns x 8 image groups x 8 row slots; row slot r walks n = r, r + 8, ..., whose
+// rows fall in row lanes (r + 15) % 16 (n = r mod 16) and (r + 7) % 16 (n = r + 8 mod 16).
+template <bool GROUPED>
+__global__ void __launch_bounds__(1024) embed_grad_accum_kernel(const float* __restrict__ dh0, int B, int N, int D,
+                                                                float* __restrict__ dpos, float* __restrict__ dcls,
+                                                                float* __restrict__ dbias, DropDev drop) {
+  __shared__ float red[8][8][16];
+  __shared__ float lanes[16][17];
+  const int c = threadIdx.x & 15, grp = (threadIdx.x >> 4) & 7, r = threadIdx.x >> 7;
+  const int d = blockIdx.x * 16 + c;
+  float b0 = 0.f, b1 = 0.f;  // bias sums of the rows n = r (mod 16) and n = r + 8 (mod 16)
+  for (int j = 0; j * 8 < N; ++j) {
+    const int n = r + 8 * j;
+    float s = 0.f;
+    if (d < D && n < N && (GROUPED || grp == 0)) {
+      const int step = GROUPED ? 8 : 1;
+      if (drop.thr) {  // gradient through the position-embedding dropout
+        for (int b = grp; b < B; b += step) {
+          float v = dh0[((long)b * N + n) * D + d];
+          v *= drop_mult1(drop, (long)b * N + n, d);
+          s += v;
+        }
+      } else {
+        for (int b = grp; b < B; b += step) s += dh0[((long)b * N + n) * D + d];
+      }
+    }
+    red[r][grp][c] = s;
+    __syncthreads();
+    if (grp == 0 && d < D && n < N) {
+      if (GROUPED) {
+#pragma unroll
+        for (int k = 1; k < 8; ++k) s += red[r][k][c];
+      }
+      dpos[(long)n * D + d] += s;
+      if (n == 0)
+        dcls[d] += s;
+      else if (j & 1)
+        b1 += s;
+      else
+        b0 += s;
+    }
+    __syncthreads();
+  }
+  if (grp == 0) {
+    lanes[(r + 15) & 15][c] = b0;
+    lanes[(r + 7) & 15][c] = b1;
+  }
+  __syncthreads();
+  if (threadIdx.x < 16 && d < D) {
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t += lanes[k][c];
+    dbias[d] += t;
+  }
+}
+
 // ---- column sums --------------------------------------------------------------------------------
 // Vector path: a thread owns 8 consecutive columns (one 16-B bf16 / 32-B f32 load per row), a
 // 256-thread block = 32 column groups x 8 row lanes; each block reduces a chunk of rows into one
@@ -523,6 +587,24 @@ extern "C" int vit_embed_grad(const float* dh0, int64_t B, int64_t N, int64_t D,
   hipLaunchKernelGGL(cls_bias_grad16_kernel, dim3((unsigned)((D + 15) / 16)), dim3(256), 0, s, dpos, (int)N, (int)D,
                      dcls, dconv_bias);
   VIT_LAUNCH_CHECK("vit_embed_grad");
+}
+
+extern "C" int vit_embed_grad_accum(const float* dh0, int64_t B, int64_t N, int64_t D, float* dpos, float* dcls,
+                                    float* dconv_bias, const vit_dropout* dropout, int32_t accumulate,
+                                    vit_stream_t stream) {
+  if (!accumulate) return vit_embed_grad(dh0, B, N, D, dpos, dcls, dconv_bias, dropout, stream);
+  VIT_CHECK_ARG(dh0 && dpos && dcls && dconv_bias && B > 0 && N > 0 && D > 0, "vit_embed_grad_accum: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  // the summation order of the kernel vit_embed_grad picks for these arguments (embed_grad_accum_kernel)
+  const bool grouped = D % 4 == 0 && ((uintptr_t)dh0 % 16) == 0 && ((uintptr_t)dpos % 16) == 0;
+  const dim3 grid((unsigned)((D + 15) / 16));
+  if (grouped)
+    hipLaunchKernelGGL(embed_grad_accum_kernel<true>, grid, dim3(1024), 0, s, dh0, (int)B, (int)N, (int)D, dpos, dcls,
+                       dconv_bias, make_drop(dropout));
+  else
+    hipLaunchKernelGGL(embed_grad_accum_kernel<false>, grid, dim3(1024), 0, s, dh0, (int)B, (int)N, (int)D, dpos, dcls,
+                       dconv_bias, make_drop(dropout));
+  VIT_LAUNCH_CHECK("vit_embed_grad_accum");
 }
 
 extern "C" int64_t vit_colsum_partial_rows(int64_t rows) {

@@ -17,6 +17,8 @@
 //   * XCD-aware bijective block remap so consecutive tiles (same A rows) share an XCD's L2.
 #include "gemm_decl.h"
 
+#include <mutex>
+#include <unordered_set>
 #include <vector>
 
 namespace {
@@ -331,6 +333,13 @@ extern "C" int vit_gemm_splitk_group(const vit_gemm_args* args, int32_t n, vit_s
   return vit::check_hip(vitg::launch_splitk_group(g, (hipStream_t)stream), "vit_gemm_splitk_group launch");
 }
 
+namespace {
+// prepared tables that hold an accumulating direct member (vit_gemm_group_prepare records, vit_gemm_group_launch
+// looks up): those run on the EPI_ACC instantiation, every other table on the launch it always had
+std::mutex g_acc_tables_mu;
+std::unordered_set<const void*> g_acc_tables;
+}  // namespace
+
 extern "C" int64_t vit_gemm_group_table_bytes(int32_t n) {
   return n >= 1 && n <= vitg::GEMM_TABLE_MAX ? (int64_t)vitg::group_table_bytes(n) : 0;
 }
@@ -347,8 +356,12 @@ extern "C" int vit_gemm_group_prepare(const vit_gemm_args* args, const int32_t* 
   GemmDev* g = reinterpret_cast<GemmDev*>(host.data());
   int* start = reinterpret_cast<int*>(host.data() + soff);
   long total = 0;
+  bool any_acc = false;
   for (int i = 0; i < n; ++i) {
     const vit_gemm_args* a = args + i;
+    VIT_CHECK_ARG(!direct || (direct[i] >= 0 && direct[i] <= 2),
+                  "vit_gemm_group_prepare: direct[%d] = %d (0 slab, 1 direct, 2 direct and accumulating)", i,
+                  direct ? (int)direct[i] : 0);
     VIT_CHECK_ARG(a->epilogue == VIT_EPI_SPLITK && a->a_layout == VIT_MN_CONTIG && a->b_layout == VIT_MN_CONTIG &&
                       a->tile == 0 && !a->col_partial && !a->dropout,
                   "vit_gemm_group_prepare: member %d must be a split-K weight gradient (VIT_EPI_SPLITK, both operands "
@@ -363,6 +376,8 @@ extern "C" int vit_gemm_group_prepare(const vit_gemm_args* args, const int32_t* 
       g[i].ldc = a->ldc;
       g[i].c_bs = a->c_batch_stride;
       g[i].vec = ((uintptr_t)a->C % 32) == 0 && a->ldc % 8 == 0 && a->c_batch_stride % 8 == 0;
+      g[i].acc = direct[i] == 2;  // C = C + result (the EPI_ACC launch)
+      any_acc = any_acc || g[i].acc;
     }
     start[i] = (int)total;
     total += ((a->M + 255) / 256) * ((a->N + 255) / 256) * a->split_k * a->batch;
@@ -375,6 +390,13 @@ extern "C" int vit_gemm_group_prepare(const vit_gemm_args* args, const int32_t* 
   if (const int rc = vit::check_hip(hipMemcpy(table, host.data(), host.size(), hipMemcpyHostToDevice),
                                     "vit_gemm_group_prepare upload"))
     return rc;
+  {
+    std::lock_guard<std::mutex> lk(g_acc_tables_mu);
+    if (any_acc)
+      g_acc_tables.insert(table);
+    else
+      g_acc_tables.erase(table);
+  }
   *total_out = (int32_t)total;
   return VIT_OK;
 }
@@ -382,7 +404,12 @@ extern "C" int vit_gemm_group_prepare(const vit_gemm_args* args, const int32_t* 
 extern "C" int vit_gemm_group_launch(const void* table, int32_t n, int32_t total, vit_stream_t stream) {
   VIT_CHECK_ARG(table != nullptr && n >= 1 && n <= vitg::GEMM_TABLE_MAX && total >= 1,
                 "vit_gemm_group_launch: a prepared table, its member count and its workgroup total");
-  return vit::check_hip(vitg::launch_group_table(table, n, total, (hipStream_t)stream), "vit_gemm_group_launch");
+  bool acc;
+  {
+    std::lock_guard<std::mutex> lk(g_acc_tables_mu);
+    acc = g_acc_tables.count(table) != 0;
+  }
+  return vit::check_hip(vitg::launch_group_table(table, n, total, acc, (hipStream_t)stream), "vit_gemm_group_launch");
 }
 
 // ---- split-K reduction -------------------------------------------------------------------------

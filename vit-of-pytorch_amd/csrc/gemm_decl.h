@@ -52,6 +52,7 @@ struct GemmDev {
   int split_xcd;       // split-K grids: place each XCD's workgroups on one or two K-chunks (VIT_GEMM_SPLIT_XCD)
   int prio;            // s_setprio(1) around the ping-pong kernels' MFMA clusters (VIT_GEMM_PRIO)
   int ilv;             // diagnostic builds: gemm_pp2's interleaved read slot, -1 auto (M/N-contiguous pairs), 0 off, 1 on
+  int acc;             // direct group member of an EPI_ACC table launch: C = C + result instead of C = result
 #ifdef VIT_PP2_STAMPS
   unsigned long long* stamps;  // diagnostic build: gemm_pp2's slot stamps (VIT_GEMM_DIAG = 4, vit_gemm_set_stamps)
 #endif
@@ -72,11 +73,16 @@ hipError_t launch_splitk_group(const GemmGroup& g, hipStream_t s);
 constexpr int GEMM_TABLE_MAX = 128;
 inline size_t group_table_start_off(int n) { return ((size_t)n * sizeof(GemmDev) + 15) & ~(size_t)15; }
 inline size_t group_table_bytes(int n) { return group_table_start_off(n) + ((size_t)n + 1) * sizeof(int); }
-hipError_t launch_group_table(const void* table, int n, int total, hipStream_t s);
+// (acc: the table holds an accumulating direct member, so the EPI_ACC instantiation runs it)
+hipError_t launch_group_table(const void* table, int n, int total, bool acc, hipStream_t s);
 
 // Internal epilogue flag: the dropout variant of PATCH / BIAS_RESID_F32 / BIAS_GELU_DGELU (its own
 // instantiation, so the dropout-free kernels carry none of the Philox code)
 constexpr int EPI_DROP = 16;
+// Internal epilogue flag, VIT_EPI_SPLITK only: the table launch whose direct members may add their result into the
+// destination (GemmDev::acc, wave-uniform per member); again its own instantiation, so the overwriting launch
+// carries neither the destination reads nor the branch
+constexpr int EPI_ACC = 32;
 
 // launchers, one translation unit per epilogue (gemm_e<EPI>.hip) so the build parallelises
 template <int EPI>

@@ -7,6 +7,6 @@ template <> hipError_t vitg::launch_layout_x<7>(int cfg, const GemmDev& d, bool 
 
 hipError_t vitg::launch_splitk_group(const GemmGroup& g, hipStream_t s) { return launch_pp2_group(g, s); }
 
-hipError_t vitg::launch_group_table(const void* table, int n, int total, hipStream_t s) {
-  return launch_pp2_table(table, n, total, s);
+hipError_t vitg::launch_group_table(const void* table, int n, int total, bool acc, hipStream_t s) {
+  return acc ? launch_pp2_table<vitg::EPI_ACC>(table, n, total, s) : launch_pp2_table<0>(table, n, total, s);
 }

@@ -151,6 +151,7 @@ __device__ __forceinline__ void wait_vm() {
 }
 
 using vitg::EPI_DROP;
+using vitg::EPI_ACC;
 
 template <int EPI>
 __device__ __forceinline__ void epi_store(const GemmDev& p, int z, int split_idx, int m, int n, float v) {
@@ -211,6 +212,9 @@ __device__ __forceinline__ void epi_store(const GemmDev& p, int z, int split_idx
     // slab (z, split) at stride c_bs with row stride ldc: M * N and N for slabs, the caller's own output strides
     // for a direct member of vit_gemm_group_launch (make_dev / group_prepare set them)
     float* C = (float*)p.C + ((long)z * p.split_k + split_idx) * p.c_bs;
+    if constexpr ((EPI & EPI_ACC) != 0) {  // an accumulating direct member adds its finished value once
+      if (p.acc) v += C[(long)m * p.ldc + n];
+    }
     C[(long)m * p.ldc + n] = v;
   }
 }
@@ -381,7 +385,21 @@ __device__ __forceinline__ void epi_store8(const GemmDev& p, int z, int split_id
     }
     st8f((float*)p.C + (long)m * p.ldc + n, v, p.nt);
   } else if constexpr (E == VIT_EPI_SPLITK) {
-    st8f((float*)p.C + ((long)z * p.split_k + split_idx) * p.c_bs + (long)m * p.ldc + n, v, p.nt);
+    float* q = (float*)p.C + ((long)z * p.split_k + split_idx) * p.c_bs + (long)m * p.ldc + n;
+    if constexpr ((EPI & EPI_ACC) != 0) {
+      if (p.acc) {  // the old values: prefetched by the caller (AuxPre), or read here
+        float r[8];
+        if (pre) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) r[k] = pre[k];
+        } else {
+          ld8f(q, r);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] += r[k];
+      }
+    }
+    st8f(q, v, p.nt);
   }
 }
 
@@ -419,6 +437,13 @@ __device__ __forceinline__ void epi_prep8(const GemmDev& p, int m, int n, float*
   constexpr int E = EPI & 15;
   constexpr bool DROP = (EPI & EPI_DROP) != 0;
   if constexpr (E == VIT_EPI_F32 || E == VIT_EPI_SPLITK) {
+    if constexpr ((EPI & EPI_ACC) != 0) {
+      // pre: the destination's old values (AuxPre). A select per value on the member's wave-uniform bit, no branch:
+      // branches inside the unrolled passes made the register allocator spill
+      const bool add = p.acc != 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = add ? v[k] + pre[k] : v[k];
+    }
     o[0] = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
     o[1] = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
   } else if constexpr (E == VIT_EPI_BF16) {
@@ -514,11 +539,21 @@ __device__ __forceinline__ void epi_put8(const GemmDev& p, int z, int split_idx,
 template <int EPI>
 struct AuxPre {
   static constexpr int E = EPI & 15;
+  static constexpr bool ACC = E == VIT_EPI_SPLITK && (EPI & vitg::EPI_ACC) != 0;
   static constexpr int W = (E == VIT_EPI_GELU_BWD || E == VIT_EPI_MUL_BF16) ? 1
-                           : E == VIT_EPI_BIAS_RESID_F32                      ? 2
+                           : (E == VIT_EPI_BIAS_RESID_F32 || ACC)             ? 2
                                                                                 : 0;
-  __device__ __forceinline__ static void fetch(const GemmDev& p, int m, int n, uint4* d) {
-    if constexpr (W == 1) {
+  // z: the batch index (read by the accumulating variant only, whose operand is the output itself)
+  __device__ __forceinline__ static void fetch(const GemmDev& p, int m, int n, uint4* d, int z = 0) {
+    if constexpr (ACC) {
+      // the old destination values of an accumulating direct member (split 1: batch z lies at z c_bs, and
+      // split_idx is 0 for every member this is called for). Called on the whole-tile path only, where the words
+      // lie inside the member's own output; the other members of the table fetch theirs too and do not use them
+      // (epi_prep8), which keeps the unrolled passes free of branches
+      const float* a = (const float*)p.C + (long)z * p.c_bs + (long)m * p.ldc + n;
+      d[0] = *reinterpret_cast<const uint4*>(a);
+      d[1] = *reinterpret_cast<const uint4*>(a + 4);
+    } else if constexpr (W == 1) {
       d[0] = *reinterpret_cast<const uint4*>((const bf16_t*)p.aux + (long)m * p.ldaux + n);
     } else if constexpr (W == 2) {
       const float* a = (const float*)p.aux + (long)m * p.ldaux + n;
@@ -551,7 +586,10 @@ __device__ __forceinline__ void epilogue_fast(const GemmDev& p, v4f (&acc)[8][FN
   constexpr int W = EpiOut<EPI>::W;
   constexpr int AW = AuxPre<EPI>::W > 0 ? AuxPre<EPI>::W : 1;
   constexpr int PF = 16, ITF = PF * CPR / 64, NPF = 8;
-  constexpr int NSET = W == 2 ? 4 : NPF;  // output register sets (ring of passes)
+  // output register sets (ring of passes). The accumulating variant keeps 2: its wait for the next pass's old values
+  // (requested after the previous pass's stores; vmcnt retires in order) has already retired the stores of the set
+  // it reuses, so a deeper ring would buy nothing for its 32 registers
+  constexpr int NSET = (EPI & EPI_ACC) ? 2 : W == 2 ? 4 : NPF;
   const int g = lane >> 4, c = lane & 15;
   const int ch = lane % CPR;
   const int n = nw0 + ch * 8;
@@ -563,7 +601,7 @@ __device__ __forceinline__ void epilogue_fast(const GemmDev& p, v4f (&acc)[8][FN
   auto fetch_f = [&](uint4 (*ax)[AW], int pass) {
     if constexpr (AuxPre<EPI>::W > 0) {
 #pragma unroll
-      for (int it = 0; it < ITF; ++it) AuxPre<EPI>::fetch(p, mw0 + pass * PF + (lane + it * 64) / CPR, n, ax[it]);
+      for (int it = 0; it < ITF; ++it) AuxPre<EPI>::fetch(p, mw0 + pass * PF + (lane + it * 64) / CPR, n, ax[it], z);
     }
   };
   fetch_f(fc, 0);

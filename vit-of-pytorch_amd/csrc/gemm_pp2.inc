@@ -359,15 +359,19 @@ __device__ __forceinline__ void pp2_tile(const GemmDev& p, const int tm, const i
   float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   constexpr int IT = PR * CPR / 64;  // 8-column chunks per lane and pass
   static_assert(IT * 64 == PR * CPR, "whole chunks per pass");
-  constexpr int AW = AuxPre<EPI>::W > 0 ? AuxPre<EPI>::W : 1;
+  // (the accumulating table launch prefetches its old destination values on the whole-tile path only; on this
+  // generic path, the edge tiles and unaligned destinations, epi_store8 reads them at store time: the 16 words of
+  // prefetch registers per lane beside the live accumulators would spill)
+  constexpr int GW = (EPI & EPI_ACC) ? 0 : AuxPre<EPI>::W;
+  constexpr int AW = GW > 0 ? GW : 1;
   uint4 axc[IT][AW], axn[IT][AW];  // aux chunks of this pass / the next one
   auto fetch_pass = [&](uint4 (*ax)[AW], int pass) {
-    if constexpr (AuxPre<EPI>::W > 0) {
+    if constexpr (GW > 0) {
 #pragma unroll
       for (int it = 0; it < IT; ++it) {
         const int e = lane + it * 64, row = e / CPR, ch = e % CPR;
         const int m = m0 + wm0 + pass * PR + row, n = n0 + wn0 + ch * 8;
-        if (p.vec && m < p.M && n + 8 <= p.N) AuxPre<EPI>::fetch(p, m, n, ax[it]);
+        if (p.vec && m < p.M && n + 8 <= p.N) AuxPre<EPI>::fetch(p, m, n, ax[it], z);
       }
     }
   };
@@ -394,7 +398,7 @@ __device__ __forceinline__ void pp2_tile(const GemmDev& p, const int tm, const i
       ld8f(ws + row * LDW + ch * 8, v);
       if (m >= p.M || n >= p.N || p.diag == 1 || (p.diag == 3 && (blockIdx.x & 1))) continue;
       if (p.vec && n + 8 <= p.N) {
-        if constexpr (AuxPre<EPI>::W > 0) {
+        if constexpr (GW > 0) {
           float u[8];
           AuxPre<EPI>::unpack(axc[it], u);
           epi_store8<EPI>(p, z, split_idx, m, n, v, u);
@@ -412,7 +416,7 @@ __device__ __forceinline__ void pp2_tile(const GemmDev& p, const int tm, const i
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    if constexpr (AuxPre<EPI>::W > 0) {
+    if constexpr (GW > 0) {
 #pragma unroll
       for (int it = 0; it < IT; ++it)
 #pragma unroll
@@ -499,7 +503,10 @@ __global__ void __launch_bounds__(512) gemm_pp2_group_kernel(const GemmGroup G) 
 // share its operand panels) are adjacent positions of one XCD. Assumed about dispatch, for speed only: launch
 // indices are dealt to the 8 XCDs in turn and start in order, so in every round an XCD's CUs hold a run of
 // neighbouring positions. No workgroup waits for another; a different dispatch order costs L2 hits, not results.
-template <bool AK, bool BKC>
+// ACC = EPI_ACC: the instantiation whose direct members with GemmDev::acc set add into their destination (each
+// output element belongs to one workgroup at split 1, so the read-modify-write needs no atomics and is deterministic);
+// its slab members and plain direct members store as in the ACC = 0 instantiation.
+template <bool AK, bool BKC, int ACC = 0>
 __global__ void __launch_bounds__(512) gemm_pp2_table_kernel(const GemmDev* __restrict__ tab,
                                                              const int* __restrict__ start, const int n) {
   const int orig = blockIdx.x;
@@ -518,7 +525,7 @@ __global__ void __launch_bounds__(512) gemm_pp2_table_kernel(const GemmDev* __re
   const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
   int tm, tn, z, split_idx;
   splitk_coords(p, w - start[gi], tiles_m * tiles_n, tiles_m, tiles_n, tm, tn, z, split_idx);
-  pp2_tile<AK, BKC, VIT_EPI_SPLITK>(p, tm, tn, z, split_idx, orig);
+  pp2_tile<AK, BKC, VIT_EPI_SPLITK | ACC>(p, tm, tn, z, split_idx, orig);
 }
 
 template <bool AK, bool BKC, int EPI, int BK = 64, int NA = 2>
@@ -536,9 +543,10 @@ inline hipError_t launch_pp2_group(const GemmGroup& g, hipStream_t s) {
 }
 
 // ... with the members in a device table of n descriptors and n + 1 starts (total = start[n] workgroups)
-inline hipError_t launch_pp2_table(const void* table, int n, int total, hipStream_t s) {
+template <int ACC>
+hipError_t launch_pp2_table(const void* table, int n, int total, hipStream_t s) {
   const GemmDev* tab = (const GemmDev*)table;
   const int* start = (const int*)((const char*)table + vitg::group_table_start_off(n));
-  hipLaunchKernelGGL((gemm_pp2_table_kernel<false, false>), dim3(total), dim3(512), 0, s, tab, start, n);
+  hipLaunchKernelGGL((gemm_pp2_table_kernel<false, false, ACC>), dim3(total), dim3(512), 0, s, tab, start, n);
   return hipGetLastError();
 }

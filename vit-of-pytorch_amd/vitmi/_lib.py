@@ -17,7 +17,7 @@ c_i32 = ctypes.c_int32
 c_f32 = ctypes.c_float
 c_vp = ctypes.c_void_p
 
-ABI_VERSION = 22  # vit_abi_version() of the library these prototypes describe
+ABI_VERSION = 23  # vit_abi_version() of the library these prototypes describe
 
 # enum vit_layout / vit_epilogue (include/vit_hip.h)
 K_CONTIG, MN_CONTIG = 0, 1
@@ -128,6 +128,8 @@ _SIGS = {
     "vit_preprocess_u8_ragged": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
                                          c_vp, c_vp]),
     "vit_embed_grad": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(Dropout), c_vp]),
+    "vit_embed_grad_accum": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(Dropout), c_i32,
+                                     c_vp]),
     "vit_dropout_mask": (c_i32, [ctypes.POINTER(Dropout), c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "vit_colsum_partial_rows": (c_i64, [c_i64]),
     "vit_colsum": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp]),

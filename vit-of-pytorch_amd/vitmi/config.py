@@ -13,6 +13,9 @@ src/config.py:57-104). Additions for the MI355X path, all optional:
                          (vitmi.checkpoint.resize_pos_embedding)
   --no-save              do not create experiments/ directories or checkpoints
   --precision            (eval) bf16 MFMA forward (default) or the reference's f32 arithmetic
+  --accum-steps K        (train) every optimizer step as K micro-batches of batch / (K * n_gpu) images, gradients
+                         accumulated in the kernels; --batch-size stays the batch of one optimizer step
+  --clip-grad-norm X     (train) clip the step's gradient to global 2-norm X (0: off)
 
 Without --synthetic, the reference's own commands run on CIFAR read from disk (vitmi.datasets, vitmi.data):
     python -m vitmi.train --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path w.pth ...
@@ -128,8 +131,16 @@ def get_train_config(argv=None):
     parser.add_argument("--warmup-steps", type=int, default=500, help="learning rate warm up steps")
     parser.add_argument("--dataset", type=str, default="CIFAR100", help="dataset for fine-tunning/evaluation")
     parser.add_argument("--no-save", default=False, action="store_true", help="no experiment dirs / checkpoints")
+    parser.add_argument("--accum-steps", type=int, default=1,
+                        help="micro-batches per optimizer step (gradient accumulation); --batch-size stays the "
+                             "batch of one optimizer step")
+    parser.add_argument("--clip-grad-norm", type=float, default=0.0,
+                        help="clip the gradient to this global 2-norm before each update (0: off)")
     config = parser.parse_args(argv)
     _check_image_size(config)
+    if config.accum_steps < 1 or config.batch_size % (config.accum_steps * max(1, config.n_gpu)):
+        raise SystemExit(f"--batch-size {config.batch_size} is the batch of one optimizer step and must divide evenly "
+                         f"into --accum-steps {config.accum_steps} micro-batches on each of {config.n_gpu} GPUs")
     config = globals()["get_{}_config".format(config.model_arch)](config)
     process_config(config)
     print_config(config)

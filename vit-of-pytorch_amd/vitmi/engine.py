@@ -251,9 +251,10 @@ class _BiasReducer:
     wanted. The partial buffers rotate through rings of _NBUF (> the reductions queued between flushes),
     all in compute-stream order."""
 
-    def __init__(self, eng, a):
+    def __init__(self, eng, a, accumulate=False):
         self.eng = eng
         self.a = a
+        self.accumulate = accumulate  # every reduction adds its finished sums into its outputs
         self.D = eng.cfg.emb_dim
         self.nxt = {}
         self.queued = {}  # kind -> partial buffers of that kind written since the last flush
@@ -271,7 +272,7 @@ class _BiasReducer:
 
     def reduce(self, part, rows, cols, ld, outs, seg=0):
         """queue out_k[c - k*seg] = sum_r part[r*ld + c] (seg = 0: one output)"""
-        self.jobs.append((part, rows, cols, ld, seg, outs, False))
+        self.jobs.append((part, rows, cols, ld, seg, outs, self.accumulate))
         if len(self.jobs) == ops.COLSUM_BATCH_MAX:
             self.flush()
 
@@ -298,10 +299,12 @@ class _WgradQueue:
     defer == 0: with `group`, a spec pushed with hold=True shares the next push's launch (a layer's out-projection and
     q|k|v: one wave instead of two short grids); every other spec runs at once on the single form.
     Launches go through `on_side` (the side stream under ViTEngine.overlap_wgrad); a spec's `done` runs once the launch
-    that reads its operands is issued (the backward's buffer releases)."""
+    that reads its operands is issued (the backward's buffer releases). accumulate: every spec adds into its
+    destination (the reductions' flag; a direct table member's accumulating epilogue)."""
 
-    def __init__(self, eng, K, on_side, defer, group):
+    def __init__(self, eng, K, on_side, defer, group, accumulate=False):
         self.eng, self.K, self.on_side, self.defer, self.group = eng, K, on_side, defer, group
+        self.accumulate = accumulate
         self.recorded, self.layers, self.launches = [], 0, 0  # deferred: (spec, done) of the next table launch
         self.held = []                                        # grouped: (spec, done) waiting for the next push
 
@@ -314,21 +317,25 @@ class _WgradQueue:
 
     def single(self, spec, K=None, done=None):
         """launch now, on its own (K: the cls-row gradients' own row count)"""
-        self._run(wgrad.single, spec, K=K, done=(done,))
+        self._run(wgrad.single, self._acc(spec), K=K, done=(done,))
+
+    def _acc(self, spec):
+        return spec._replace(accumulate=True) if self.accumulate else spec
 
     def push(self, spec, done=None, hold=False):
+        spec = self._acc(spec)
         if self.defer:
             if spec.M >= 256 and spec.N >= 256:
                 self.recorded.append((spec, done))
             else:
-                self.single(spec, done=done)
+                self._run(wgrad.single, spec, done=(done,))
         elif self.group and (hold or self.held):
             self.held.append((spec, done))
             if not hold:
                 (specs, dones), self.held = zip(*self.held), []
                 self._run(wgrad.group, specs, True, done=dones)
         else:
-            self.single(spec, done=done)
+            self._run(wgrad.single, spec, done=(done,))
 
     def end_layer(self, i):
         self.layers += 1
@@ -339,7 +346,11 @@ class _WgradQueue:
         recorded, self.recorded, self.layers = self.recorded, [], 0
         if recorded:
             specs, dones = zip(*recorded)
-            self._run(wgrad.table, specs, self.eng._wgrad_tables, (self.eng._last_b, self.launches), done=dones)
+            # (an accumulating backward's slots name the flag: the micro-step that overwrites and the ones that
+            #  accumulate each keep their prepared tables, instead of rebuilding each other's, with a stream
+            #  synchronisation, every time)
+            slot = (self.eng._last_b, True, self.launches) if self.accumulate else (self.eng._last_b, self.launches)
+            self._run(wgrad.table, specs, self.eng._wgrad_tables, slot, done=dones)
             self.launches += 1
 
 
@@ -402,7 +413,9 @@ class ViTEngine:
         # VITMI_WGRAD_DEFER: 0 = the per-layer path, N > 0 = layers per launch, "all" (default) = one launch.
         v = os.environ.get("VITMI_WGRAD_DEFER", "all")
         self.wgrad_defer = L if v == "all" else int(v)
-        self._wgrad_tables = {}  # ((batch size, launch of the backward), first member) -> wgrad.table's entry
+        # ((batch size, launch of the backward), first member) -> wgrad.table's entry; an accumulating backward's
+        # slots are (batch size, True, launch)
+        self._wgrad_tables = {}
         # Only the cls token of the last layer's output reaches the classifier (src/model.py:210),
         # so that layer's out-projection, LayerNorm 2 and MLP (forward and backward) run on the b cls
         # rows and its attention on the first 32-query pair of each (image, head) (q_rows = 1); the
@@ -663,9 +676,11 @@ class ViTEngine:
         return a.dlogits, a.row_stats
 
     # ---- backward --------------------------------------------------------------------------------
-    def backward(self, dlogits: torch.Tensor, grad: torch.Tensor | None = None):
+    def backward(self, dlogits: torch.Tensor, grad: torch.Tensor | None = None, accumulate: bool = False):
         """Backward of the last forward given dL/dlogits [b, C]; writes every parameter gradient
-        into `grad` (default self.grad, flat layout).
+        into `grad` (default self.grad, flat layout). accumulate: adds them into `grad` instead (gradient
+        accumulation over micro-batches): every producer adds its finished f32 value once, so the result is bit for
+        bit the overwriting backward's gradient added to what `grad` held.
 
         Two streams: the main stream runs the data-gradient chain (dgrad GEMMs, LayerNorm and
         attention backward); the weight-gradient GEMMs, which nothing downstream waits for, run on
@@ -732,12 +747,12 @@ class ViTEngine:
         group = self.group_wgrad and D >= 256  # (the grouped kernel takes M, N >= 256)
         # deferred weight gradients (wgrad_defer layers per launch), unless something wants a layer's gradients early
         defer = self.wgrad_defer if not hook and not overlap and D >= 256 and M >= 256 else 0
-        wq = _WgradQueue(self, a.Tp, on_side, defer, group)
+        wq = _WgradQueue(self, a.Tp, on_side, defer, group, accumulate)
         dhbs, dgs, dqkvs = a.defer_bufs() if defer else (a.dhb, a.dg, a.dqkv)
         nd = len(dhbs)
-        bias = _BiasReducer(self, a)
+        bias = _BiasReducer(self, a, accumulate)
         # classifier head (f32): dWc = dl^T lncls, dbc = colsum(dl), dlncls = dl Wc
-        ops.gemm_f32(C, D, b, dl, C, True, a.lncls, D, False, gv("classifier.weight"), D)
+        ops.gemm_f32(C, D, b, dl, C, True, a.lncls, D, False, gv("classifier.weight"), D, accumulate=accumulate)
         bias.reduce(dl, b, C, C, (gv("classifier.bias"),))
         ops.gemm_f32(b, D, C, dl, C, False, f[self.off("classifier.weight"):], D, False, a.dlncls, D)
         # final LN backward on cls rows -> residual grad (zero elsewhere)
@@ -818,7 +833,7 @@ class ViTEngine:
         wq.push(Spec(dhbs[wb], D, a.patches, a.kpad, D, cfg.patch_k, gv("embedding.weight"), cfg.patch_k))
         wq.finish()  # after the last data gradient; the bias and column reductions follow
         ops.embed_grad(a.dh, b, N, D, gv("transformer.pos_embedding.pos_embedding"), gv("cls_token"),
-                       gv("embedding.bias"), dropout=dd(0))
+                       gv("embedding.bias"), dropout=dd(0), accumulate=accumulate)
         fire(self.layout.buckets[-1])
         bias.flush()
         if overlap:

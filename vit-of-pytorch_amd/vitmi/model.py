@@ -16,6 +16,8 @@ on a ROCm GPU.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -200,6 +202,15 @@ class _ViTFunction(torch.autograd.Function):
             raise RuntimeError("vitmi: backward of a stale forward (another forward ran on this model since); "
                                "the engine keeps one set of saved activations per batch size")
         params = model._flat_params
+        if model.accumulate_in_place and all(
+                p.grad is not None and p.grad.data_ptr() == eng.layout.view(eng.grad, n).data_ptr()
+                for n, p in zip(model._flat_names, params)):
+            # gradient accumulation in the kernels: every .grad is the engine's own flat-gradient view (what the
+            # first micro-step left), so this backward adds into it and autograd gets nothing to add
+            eng.backward(dlogits, eng.grad, accumulate=True)
+            if eng.grad_ready_finish is not None:
+                eng.grad_ready_finish()
+            return (None, None, *([None] * len(params)))
         accumulate = any(p.grad is not None for p in params)
         if accumulate:
             buf = model._scratch_grad()
@@ -244,6 +255,27 @@ class VisionTransformer(nn.Module):
         self._flat_names = None
         self._flat_params = None
         self._scratch = None
+        # True: a backward that finds every .grad to be the engine's flat-gradient view accumulates into it inside the
+        # kernels (ViTEngine.backward(accumulate=True)): no scratch buffer, no autograd add per parameter. False: a
+        # second backward goes through the scratch buffer and autograd's adds.
+        self.accumulate_in_place = False
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        """DistributedDataParallel.no_sync's meaning: backwards inside the context keep their gradients local (the
+        engine's grad_ready_hook / grad_ready_finish are not called), so under gradient accumulation the all-reduce
+        runs once per optimizer step, on the first backward after the context, over the accumulated sums. The hooks
+        are restored on exit, also after an exception."""
+        eng = self._engine
+        if eng is None:
+            yield
+            return
+        saved = eng.grad_ready_hook, eng.grad_ready_finish
+        eng.grad_ready_hook = eng.grad_ready_finish = None
+        try:
+            yield
+        finally:
+            eng.grad_ready_hook, eng.grad_ready_finish = saved
 
     # ---- engine binding -----------------------------------------------------------------------
     def _bind_engine(self):

@@ -310,7 +310,12 @@ def preprocess_u8_ragged(bytes, geom, out, index=None, flips=None, mean=(0.5, 0.
           "vit_preprocess_u8_ragged")
 
 
-def embed_grad(dh0, B, N, D, dpos, dcls, dconv_bias, dropout=None):
+def embed_grad(dh0, B, N, D, dpos, dcls, dconv_bias, dropout=None, accumulate=False):
+    """accumulate: dpos, dcls and dconv_bias each get their sum added once (vit_embed_grad_accum)"""
+    if accumulate:
+        check(lib().vit_embed_grad_accum(_p(dh0), B, N, D, _p(dpos), _p(dcls), _p(dconv_bias), _dp(dropout), 1,
+                                         _stream()), "vit_embed_grad_accum")
+        return
     check(lib().vit_embed_grad(_p(dh0), B, N, D, _p(dpos), _p(dcls), _p(dconv_bias), _dp(dropout), _stream()),
           "vit_embed_grad")
 
@@ -665,7 +670,8 @@ class GemmGroupTable:
     """A prepared group of split-K weight-gradient GEMMs (vit_gemm_group_prepare): any number of members up to
     GEMM_TABLE_MAX in ONE launch, their descriptors in a device table that is uploaded once and launched many times.
     members: [(A, B, C, M, N, K, kwargs, direct)], kwargs as for gemm_splitk_group; a direct member (split_k 1)
-    writes C[z*c_bs + m*ldc + n] itself, the others their packed slabs. Preparing synchronises the current stream."""
+    writes C[z*c_bs + m*ldc + n] itself (direct == 2: adds into it), the others their packed slabs. Preparing
+    synchronises the current stream."""
 
     def __init__(self, members):
         n = len(members)
@@ -678,7 +684,7 @@ class GemmGroupTable:
             _chk(B, BF16, "B")
             _chk(C, F32, "C")
             arr[i] = _gemm_args(A, B, C, M, N, K, **kw)
-            direct[i] = int(bool(d))
+            direct[i] = 2 if d == 2 else int(bool(d))
         nbytes = int(lib().vit_gemm_group_table_bytes(n))
         self.table = torch.empty(nbytes, device=members[0][0].device, dtype=torch.uint8)
         total = ctypes.c_int32(0)

@@ -9,6 +9,11 @@ Fast path: when the optimizer holds exactly the parameters of one vitmi VisionTr
 param group and their gradients are the engine's flat gradient buffer, one kernel launch updates
 all parameters and refreshes the bf16 GEMM mirror in the same pass. Otherwise each parameter is
 updated by the same kernel individually.
+
+`max_grad_norm` (fast path only) clips first, as torch.nn.utils.clip_grad_norm_(params, max_norm, 2) would: the flat
+gradient's 2-norm reduced on the device, coef = min(1, max_norm / (norm + 1e-6)), the flat gradient scaled by it in
+place (so .grad is left clipped), then the step. Under data parallelism step() runs after the reduced gradients are
+complete, so every rank clips by the same norm.
 """
 from __future__ import annotations
 
@@ -21,7 +26,8 @@ from . import ops
 
 
 class SGD(torch.optim.SGD):
-    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, model=None):
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, model=None,
+                 max_grad_norm=None):
         if dampening != 0.0 or nesterov:
             raise NotImplementedError("vitmi.optim.SGD implements dampening=0, nesterov=False (the reference config)")
         super().__init__(params, lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
@@ -29,6 +35,9 @@ class SGD(torch.optim.SGD):
         self._model = model
         self._flat_buf = None
         self._flat_first = True
+        self.max_grad_norm = max_grad_norm
+        self._parts = None
+        self.last_norm = None  # device {total grad norm, clip coefficient} of the last clipped step
 
     def _flat_engine(self):
         m = self._model
@@ -56,12 +65,28 @@ class SGD(torch.optim.SGD):
                 self._flat_buf = torch.zeros_like(eng.flat)
                 for n, p in zip(self._model._flat_names, self._model._flat_params):
                     self.state[p]["momentum_buffer"] = eng.layout.view(self._flat_buf, n)
+            if self.max_grad_norm is not None:
+                # (the alignment padding of the flat gradient is zero: it adds nothing to the norm)
+                n = eng.layout.numel
+                if self._parts is None:
+                    self._parts = torch.zeros(max(1, min(1024, math.ceil(n / (256 * 4 * 16)))), device=eng.dev,
+                                              dtype=torch.float64)
+                    self.last_norm = torch.zeros(2, device=eng.dev)
+                ops.sqnorm_partial(eng.grad, n, self._parts)
+                ops.adamw_prep(self._parts, None, None, 0.0, 0.0, 0.0, float(self.max_grad_norm), None,
+                               self.last_norm)
+                ops.scale_by_coef(eng.grad, n, self.last_norm[1:])
             ops.sgd_step(eng.flat, eng.grad, self._flat_buf, eng.mirror, eng.layout.numel, g["lr"], g["momentum"],
                          g["weight_decay"], self._flat_first)
             self._flat_first = False
             eng.refresh_mirror(full=False)           # repack q/k/v (+ padded conv) from updated masters
             eng.mark_mirror_fresh(self._model._version_sig())
             return loss
+        if self.max_grad_norm is not None:
+            raise NotImplementedError(
+                "vitmi.optim.SGD(max_grad_norm=...) clips on the flat fast path only: the optimizer must hold exactly "
+                "the parameters of its `model` (one bound vitmi VisionTransformer) in one param group, and every "
+                ".grad must be the engine's flat gradient buffer")
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:

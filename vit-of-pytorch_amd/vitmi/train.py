@@ -24,9 +24,23 @@ save_model (:69-81), main (:84-194); MetricTracker / the step writer follow src/
   * loss / top-1 / top-5 come from the fused cross-entropy kernel's per-row statistics and are
     accumulated on the device, read back when printed, instead of three .item() host syncs per
     step (:29-32); the reported means are the same.
+  * `--accum-steps K` runs each optimizer step as K micro-batches of batch / (K * world) images whose gradients are
+    accumulated inside the kernels (VisionTransformer.accumulate_in_place), for batches whose activations do not fit;
+    `--batch-size`, `--train-steps`, `--warmup-steps` and the OneCycle schedule keep counting optimizer steps. The
+    loaders are built at the micro-batch size: vitmi.data.EpochPlan cuts contiguous slices of the epoch's order, so
+    the K micro-batches of step s are exactly the samples of the reference's batch s whenever the set size is a
+    multiple of the batch. At a ragged end EpochPlan's rule holds per micro-batch (a short last micro-batch is kept
+    on one GPU, split or skipped on several), and a short last group of micro-batches is still one step, each
+    micro-batch weighted by its share of the group's samples. Validation also runs at the micro-batch size (the
+    engine keeps a full activation set per batch size, so a full-size validation batch would undo the saving): the
+    validation means are over micro-batches.
+  * `--clip-grad-norm X` clips the accumulated (and, data parallel, reduced) gradient to global 2-norm X before the
+    update (vitmi.optim.SGD(max_grad_norm=X)).
 """
 from __future__ import annotations
 
+import contextlib
+import itertools
 import os
 import random
 import sys
@@ -216,8 +230,65 @@ def _rank_mean(*vals):
     return [float(v) / dist.get_world_size() for v in t]
 
 
-def train_epoch(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device=torch.device("cpu")):
-    """reference src/train.py:12-37 (one optimizer step per batch)."""
+def accum_weights(sizes):
+    """the loss weights b_i / sum_j b_j of one optimizer step's micro-batches of sizes b_i: the weighted sum of their
+    mean losses is the mean over the step's samples, also for a short last group"""
+    total = sum(sizes)
+    return [b / total for b in sizes]
+
+
+def steps_in_epoch(data_loader, accum_steps=1):
+    """optimizer steps of one epoch: ceil(len(loader) / accum_steps)"""
+    return -(-len(data_loader) // accum_steps)
+
+
+def _train_epoch_accum(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device, accum_steps):
+    """train_epoch for accum_steps > 1: every optimizer step takes up to accum_steps micro-batches"""
+    metrics.reset()
+    steps = steps_in_epoch(data_loader, accum_steps)
+    it = iter(data_loader)
+    for step_idx in range(steps):
+        group = list(itertools.islice(it, accum_steps))
+        if not group:
+            break
+        weights = accum_weights([t.shape[0] for _, t in group])
+        optimizer.zero_grad()
+        loss = acc1 = acc5 = 0.0
+        for i, ((batch_data, batch_target), w) in enumerate(zip(group, weights)):
+            batch_data = batch_data.to(device, non_blocking=True)
+            batch_target = batch_target.to(device, non_blocking=True)
+            # the gradients stay local until the step's last micro-batch (one all-reduce per optimizer step)
+            with model.no_sync() if i + 1 < len(group) else contextlib.nullcontext():
+                batch_pred = model(batch_data)
+                micro_loss = criterion(batch_pred, batch_target)
+                (micro_loss * w).backward()
+            a1, a5 = _step_accuracy(criterion, batch_pred, batch_target)
+            loss = loss + micro_loss.detach() * w
+            acc1, acc5 = acc1 + a1 * w, acc5 + a5 * w
+        optimizer.step()
+        lr_scheduler.step()
+        metrics.writer.set_step((epoch - 1) * steps + step_idx)
+        metrics.update("loss", loss)
+        metrics.update("acc1", acc1)
+        metrics.update("acc5", acc5)
+        if step_idx % 100 == 0:
+            shown = _rank_mean(loss, acc1, acc5)
+            if not dist.is_initialized() or dist.get_rank() == 0:
+                print("Train Epoch: {:03d} Batch: {:05d}/{:05d} Loss: {:.4f} Acc@1: {:.2f}, Acc@5: {:.2f}"
+                      .format(epoch, step_idx, steps, *shown), flush=True)
+    wait = getattr(data_loader, "data_wait_s", None)
+    if wait is not None and (not dist.is_initialized() or dist.get_rank() == 0):
+        print("Train Epoch: {:03d} data_wait_s: {:.3f}".format(epoch, wait), flush=True)
+    return metrics.result()
+
+
+def train_epoch(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device=torch.device("cpu"),
+                accum_steps=1):
+    """reference src/train.py:12-37 (one optimizer step per batch; accum_steps > 1: per accum_steps micro-batches of
+    the loader, their gradients accumulated and the metrics their sample-weighted means)."""
+    if accum_steps > 1:
+        return _train_epoch_accum(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device,
+                                  accum_steps)
     metrics.reset()
     for batch_idx, (batch_data, batch_target) in enumerate(data_loader):
         batch_data = batch_data.to(device, non_blocking=True)
@@ -320,6 +391,14 @@ def rank_batch(global_batch, world):
     return global_batch // world
 
 
+def micro_batch(global_batch, accum_steps, world):
+    """images per rank and micro-step: --batch-size is the batch of one optimizer step over all GPUs"""
+    if accum_steps < 1 or global_batch % (accum_steps * world):
+        raise SystemExit(f"--batch-size {global_batch} is the batch of one optimizer step and must divide evenly into "
+                         f"--accum-steps {accum_steps} micro-batches on each of {world} GPUs")
+    return global_batch // (accum_steps * world)
+
+
 def main(argv=None):
     config = get_train_config(argv)
     if "WORLD_SIZE" not in os.environ and config.n_gpu > 1:
@@ -361,7 +440,8 @@ def main(argv=None):
     if world > 1:
         from .dist import init_process_group
         init_process_group(device=device)
-    batch = rank_batch(config.batch_size, world)
+    rank_batch(config.batch_size, world)
+    batch = micro_batch(config.batch_size, config.accum_steps, world)  # the loaders' and the engine's batch size
 
     train_loader = valid_loader = None
     if not config.synthetic:
@@ -383,6 +463,7 @@ def main(argv=None):
         print("Load pretrained weights from {}".format(config.checkpoint_path))
     model = model.to(device)
     engine = model.engine()
+    model.accumulate_in_place = config.accum_steps > 1
     if world > 1:
         dist.broadcast(engine.flat, 0)  # identical replicas
         GradAllReducer(engine).attach()  # the backward returns all-reduced (averaged) gradients
@@ -404,7 +485,8 @@ def main(argv=None):
                                            seed=10_000 + config.seed + rank)
 
     criterion = CrossEntropyLoss()
-    optimizer = SGD(params=model.parameters(), lr=config.lr, weight_decay=config.wd, momentum=0.9, model=model)
+    optimizer = SGD(params=model.parameters(), lr=config.lr, weight_decay=config.wd, momentum=0.9, model=model,
+                    max_grad_norm=config.clip_grad_norm if config.clip_grad_norm > 0 else None)
     lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer=optimizer, max_lr=config.lr,
                                                        pct_start=config.warmup_steps / config.train_steps,
                                                        total_steps=config.train_steps)
@@ -413,13 +495,15 @@ def main(argv=None):
     train_metrics = MetricTracker(*metric_names, writer=writer)
     valid_metrics = MetricTracker(*metric_names, writer=writer)
     best_acc = 0.0
-    epochs = config.train_steps // len(train_loader)  # the reference's count (src/train.py:172): may be 0
+    steps_per_epoch = steps_in_epoch(train_loader, config.accum_steps)
+    epochs = config.train_steps // steps_per_epoch  # the reference's count (src/train.py:172): may be 0
     if rank == 0:
-        print(config.train_steps, len(train_loader), epochs)
+        print(config.train_steps, steps_per_epoch, epochs)
     for epoch in range(1, epochs + 1):
         log = {"epoch": epoch}
         model.train()
-        log.update(train_epoch(epoch, model, train_loader, criterion, optimizer, lr_scheduler, train_metrics, device))
+        log.update(train_epoch(epoch, model, train_loader, criterion, optimizer, lr_scheduler, train_metrics, device,
+                               accum_steps=config.accum_steps))
         model.eval()
         result = valid_epoch(epoch, model, valid_loader, criterion, valid_metrics, device)
         log.update(**{"val_" + k: v for k, v in result.items()})

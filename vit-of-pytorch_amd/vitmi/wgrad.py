@@ -37,6 +37,11 @@ class Spec(NamedTuple):
     accumulate: object = False
 
 
+# a table member's `direct` value for "direct, adding into its destination" (vit_gemm_group_prepare's direct[i] == 2);
+# plain direct members carry True, slab members False
+DIRECT_ACCUMULATE = 2
+
+
 def timed(probe, tail, fn, *args, **kw):
     """fn(*args, **kw); when `probe` is a list, between two timing events on the current stream, and
     (start, end, *tail) appended to it"""
@@ -84,15 +89,19 @@ def plan(specs, K, splits, ws, table=False):
     into it in spec order, batch * s * M * N floats each. Returns
       views    each spec's slab view of ws (None for a direct member),
       members  as ops.gemm_splitk_group takes them, (A, B, C, M, N, K, kwargs); with table=True as ops.GemmGroupTable
-               does, (..., kwargs, direct): a spec at split 1 is direct, writing out[z*out_bs + m*ldo + n] itself,
+               does, (..., kwargs, direct): a spec at split 1 is direct, writing out[z*out_bs + m*ldo + n] itself
+               (direct = DIRECT_ACCUMULATE when the spec accumulates: the launch's epilogue adds into it),
       jobs     as ops.splitk_reduce_group takes them, (ws, batch, split, M, N, out, ldo, out_bs, accumulate)."""
     views, members, jobs, o = [], [], [], 0
     for sp, s in zip(specs, splits):
         if table and s == 1:
-            if not isinstance(sp.out, torch.Tensor) or sp.accumulate:
-                raise ValueError("a direct member writes one strided destination and cannot accumulate")
+            if not isinstance(sp.out, torch.Tensor):
+                raise ValueError("a direct member writes one strided destination, not a list of per-z destinations")
+            if not isinstance(sp.accumulate, (bool, int)):
+                raise ValueError("a direct member takes one accumulate flag")
             views.append(None)
-            members.append((sp.A, sp.B, sp.out, sp.M, sp.N, K, _gemm_kw(sp, 1, sp.ldo, sp.out_bs), True))
+            members.append((sp.A, sp.B, sp.out, sp.M, sp.N, K, _gemm_kw(sp, 1, sp.ldo, sp.out_bs),
+                            DIRECT_ACCUMULATE if sp.accumulate else True))
             continue
         n = _slabs([sp], [s])
         w = ws[o:o + n]
@@ -129,7 +138,7 @@ def table(specs, K, tables, slot, alloc=None, target=256, probe=None):
     usual case: a backward's worth of tiles covers the CUs several times), else slabs and one grouped reduction after
     the last launch. tables: the caller's dict, (slot, first member) -> (key, ops.GemmGroupTable, reduce jobs); an
     entry is rebuilt (which synchronises the stream) only when its key changes: the split, K, the workspace and every
-    member's pointers, strides and shapes."""
+    member's pointers, strides, shapes and accumulate flag."""
     s = ops.splitk_factor_group([(sp.M, sp.N, sp.batch) for sp in specs], K, target)
     ws = _alloc(alloc, specs[0], _slabs(specs, [s] * len(specs))) if s > 1 else None
     jobs, o = [], 0
@@ -137,7 +146,7 @@ def table(specs, K, tables, slot, alloc=None, target=256, probe=None):
         part = specs[c0:c0 + ops.GEMM_TABLE_MAX]
         key = (s, K, o, ws.data_ptr() if s > 1 else 0) + tuple(
             (sp.A.data_ptr(), sp.lda, sp.B.data_ptr(), sp.ldb, sp.M, sp.N, sp.out.data_ptr(), sp.ldo, sp.batch, sp.a_bs,
-             sp.b_bs, sp.out_bs) for sp in part)
+             sp.b_bs, sp.out_bs, bool(sp.accumulate)) for sp in part)
         ent = tables.get((slot, c0))
         if ent is None or ent[0] != key:
             _, members, red = plan(part, K, [s] * len(part), ws[o:] if s > 1 else None, table=True)
