@@ -340,6 +340,38 @@ int vit_preprocess_u8_ragged(const uint8_t* bytes, int64_t n_bytes, const int64_
                              const float* mean_std, float* out, const int64_t* labels_in, int64_t* labels_out,
                              vit_stream_t stream);
 
+/* (ABI 24) vit_preprocess_u8_ragged with a crop box per output: torchvision's RandomResizedCrop / resized_crop
+ * inside the same launch. crops: device int64 [B][4], row b = (top, left, h, w), indexed by the OUTPUT image b as
+ * flips is. out[b] = Pillow crop((left, top, left+w, top+h)).resize((out_w, out_h), BILINEAR) of source image
+ * index[b], bit for bit, then flip and normalisation: the ragged resize run on the sub-rectangle, both axes built
+ * from (h, w), the first pixel moved by (top*W + left)*3 bytes and the row pitch staying the whole image's 3*W. The
+ * path (3 / 5 / 9-tap tiled, per pixel) is chosen from the crop's two ratios. crops == NULL is
+ * vit_preprocess_u8_ragged: the same kernel, the same launch, the same bits.
+ * A bad crop is never read through: h <= 0, w <= 0, top < 0, left < 0, top + h > H or left + w > W fill out[b] with
+ * NaN and set labels_out[b] = -1, for that output alone, as a bad table row does. Every other argument, and what
+ * the host refuses, as vit_preprocess_u8_ragged. */
+int vit_preprocess_u8_ragged_crop(const uint8_t* bytes, int64_t n_bytes, const int64_t* geom, int64_t n_images,
+                                  const int64_t* index, int64_t B, const uint8_t* flips, const int64_t* crops,
+                                  int64_t out_h, int64_t out_w, const float* mean_std, float* out,
+                                  const int64_t* labels_in, int64_t* labels_out, vit_stream_t stream);
+
+/* (ABI 24) Mixup / CutMix over a finished batch (timm's Mixup in batch mode), one HBM-bound pass: two reads and one
+ * write. x, out: f32 NCHW [B, 3, H, W], contiguous; out must not overlap x. pair: device int64 [B], the partner of
+ * each sample; lam: device float [B] in [0, 1]; box: device int64 [B][4] = (y0, y1, x0, x1), half-open. For pixel
+ * (y, x) of every channel of sample b:
+ *   y0 <= y < y1 and x0 <= x < x1     out = x[pair[b]]                                  an exact copy
+ *   elsewhere                         out = lam[b]*x[b] + (1 - lam[b])*x[pair[b]]
+ * within 2^-23 (|lam a| + |(1-lam) b|) of the exact value (1 - lam is carried with its rounding error; one rounding
+ * of the partner's term, one of the sum); lam == 1 copies x[b] and lam == 0 copies the partner, bit for bit. An
+ * empty box with lam < 1 is Mixup, a box with lam == 1 is CutMix, an empty box with lam == 1 leaves the sample
+ * alone. A box may reach outside the image. pair[b] outside [0, B) is never read through: sample b alone is NaN.
+ * 16-byte accesses when W % 4 == 0 and both pointers are 16-B aligned (the box edge is decided per element inside
+ * a vector), scalar accesses otherwise.
+ * A NULL pointer; B, H or W <= 0; H or W >= 2^15, B >= 2^31 or 3*B*H*W >= 2^40; out overlapping x:
+ * VIT_ERR_INVALID_ARG, nothing launched. */
+int vit_mix_batch(const float* x, float* out, int64_t B, int64_t H, int64_t W, const int64_t* pair,
+                  const float* lam, const int64_t* box, vit_stream_t stream);
+
 /* token-level grads of the embedding (src/model.py:17,203-204): from dh0 f32 [B*N, D]:
  * dpos[n][d] = sum_b dh0[b*N+n][d]; dcls = dpos[0]; dconv_bias = sum_{n>=1} dpos[n].
  * dropout (optional): dh0 is taken through the position-embedding dropout's multipliers first. */
@@ -398,6 +430,21 @@ int vit_gemm_f32(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, i
  * A label outside [0, C) is not read through: that row's loss and dlogits are NaN and it is a miss. */
 int vit_cross_entropy(const float* logits, const int64_t* labels, int64_t B, int64_t C,
                       float* dlogits, float grad_scale, float* row_stats, vit_stream_t stream);
+/* (ABI 24) The same launch (one block per row) against a soft target: label smoothing over a Mixup / CutMix pair,
+ * torch's cross_entropy(label_smoothing=eps) and timm's mixup_target + SoftTargetCrossEntropy.
+ * labels2: device int64 [B], the partner's label, or NULL = labels; lam: device float [B], or NULL = 1;
+ * smoothing: eps in [0, 1). With y = labels[b], y2 = labels2[b], l = lam[b]:
+ *   t_c       = (1-eps) (l [c == y] + (1-l) [c == y2]) + eps / C
+ *   loss      = lse - (1-eps) (l x_y + (1-l) x_y2) - eps mean_c x_c
+ *   dlogits_c = (p_c - t_c) grad_scale
+ * The sum of the logits rides the pass that sums the exponentials. Hits are counted against `labels`, the sample's
+ * own label, by vit_cross_entropy's rule. Either label outside [0, C): the row's loss and dlogits are NaN and it is
+ * a miss; a NaN logit as in vit_cross_entropy. A term of weight zero is left out, not multiplied by zero, so with
+ * labels2 == NULL, lam == NULL and smoothing == 0 every output is vit_cross_entropy's, bit for bit.
+ * smoothing outside [0, 1) (or NaN): VIT_ERR_INVALID_ARG, nothing launched. */
+int vit_cross_entropy_soft(const float* logits, const int64_t* labels, const int64_t* labels2, const float* lam,
+                           float smoothing, int64_t B, int64_t C, float* dlogits, float grad_scale,
+                           float* row_stats, vit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer / parameter mirrors.  torch.optim.SGD step, src/train.py:24,154-158:

@@ -398,18 +398,32 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(int M, int N, int K, cons
 }
 
 // ---- cross entropy + top-1/top-5 (src/train.py:22, src/utils.py:28-41) -------------------------
+// SOFT (vit_cross_entropy_soft): the target is t_c = (1-eps)(lam [c=y] + (1-lam) [c=y2]) + eps/C, label smoothing over
+// a Mixup / CutMix pair (torch's cross_entropy(label_smoothing=eps); timm's mixup_target + SoftTargetCrossEntropy):
+//   loss = lse - (1-eps)(lam x_y + (1-lam) x_y2) - eps mean_c x_c,   dlogits_c = (p_c - t_c) grad_scale.
+// The sum of the logits rides the pass that sums the exponentials. The three weights of the target are formed in
+// double and t_c and the loss are rounded to f32 once each (a few double operations per element of a row that is
+// read from HBM: free), so forming the target costs one rounding. A term whose weight is zero is left out instead
+// of multiplied by zero, so with lam = 1 and eps = 0 every output is the hard kernel's, bit for bit, whatever the
+// logits.
+// !SOFT is vit_cross_entropy as it always was: the soft operands are never read.
+template <bool SOFT>
 __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                 int C, float* __restrict__ dlogits, float grad_scale,
-                                                 float* __restrict__ row_stats) {
+                                                 const int64_t* __restrict__ labels2, const float* __restrict__ lam,
+                                                 float smoothing, int C, float* __restrict__ dlogits,
+                                                 float grad_scale, float* __restrict__ row_stats) {
   __shared__ float red[4];
   __shared__ float red2[4];
+  __shared__ float red3[4];
   const int b = blockIdx.x;
   const float* x = logits + (long)b * C;
   const int64_t y64 = labels[b];
+  const int64_t y2_64 = SOFT && labels2 ? labels2[b] : y64;
   // a label outside [0, C) (torch's CrossEntropyLoss raises) is never dereferenced: the row's loss and
   // gradient become NaN instead
-  const bool ok = y64 >= 0 && y64 < C;
+  const bool ok = y64 >= 0 && y64 < C && y2_64 >= 0 && y2_64 < C;
   const int y = ok ? (int)y64 : 0;
+  const int y2 = ok ? (int)y2_64 : 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float mx = -INFINITY;
   for (int c = threadIdx.x; c < C; c += 256) mx = fmaxf(mx, x[c]);
@@ -421,30 +435,53 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
   const float xy = ok ? x[y] : __builtin_nanf("");
   // rank of the label: the other classes above it. A NaN logit ranks above every number (torch.topk's order, which
   // the reference's accuracy() uses), so a diverged row is a miss, not a hit; ties count for the label
-  float s = 0.f, gt = 0.f;
+  float s = 0.f, gt = 0.f, sx = 0.f;
   for (int c = threadIdx.x; c < C; c += 256) {
     const float xc = x[c];
     s += __expf(xc - mx);
     gt += c != y && (xc > xy || __builtin_isnan(xc)) ? 1.f : 0.f;
+    if (SOFT) sx += xc;
   }
   s = wave_sum(s);
   gt = wave_sum(gt);
+  if (SOFT) sx = wave_sum(sx);
   if (lane == 0) {
     red[wave] = s;
     red2[wave] = gt;
+    if (SOFT) red3[wave] = sx;
   }
   __syncthreads();
   s = red[0] + red[1] + red[2] + red[3];
   gt = red2[0] + red2[1] + red2[2] + red2[3];
   const float lse = mx + logf(s);
+  // the target's three weights: the sample's own label, its partner's, and every class's share of the smoothing
+  double wy = 1.0, wy2 = 0.0, wu = 0.0;
+  if (SOFT) {
+    const double l = lam ? (double)lam[b] : 1.0;
+    wy = (1.0 - (double)smoothing) * l;
+    wy2 = (1.0 - (double)smoothing) * (1.0 - l);
+    wu = (double)smoothing / (double)C;
+  }
+  const bool hard = wy == 1.0 && wy2 == 0.0 && wu == 0.0;
   if (dlogits) {
     for (int c = threadIdx.x; c < C; c += 256) {
       const float p = __expf(x[c] - lse);
-      dlogits[(long)b * C + c] = ok ? (p - (c == y ? 1.f : 0.f)) * grad_scale : __builtin_nanf("");
+      float t = c == y ? 1.f : 0.f;
+      if (SOFT) t = (float)((c == y ? wy : 0.0) + (c == y2 ? wy2 : 0.0) + wu);
+      dlogits[(long)b * C + c] = ok ? (p - t) * grad_scale : __builtin_nanf("");
     }
   }
   if (threadIdx.x == 0 && row_stats) {
-    row_stats[b * 3 + 0] = lse - xy;
+    float loss = lse - xy;
+    if (SOFT && !hard) {
+      sx = red3[0] + red3[1] + red3[2] + red3[3];
+      double acc = (double)lse;
+      if (wy != 0.0) acc -= wy * (double)xy;
+      if (wy2 != 0.0) acc -= wy2 * (double)(ok ? x[y2] : __builtin_nanf(""));
+      if (wu != 0.0) acc -= wu * (double)sx;
+      loss = ok ? (float)acc : __builtin_nanf("");
+    }
+    row_stats[b * 3 + 0] = loss;
     row_stats[b * 3 + 1] = ok && gt < 1.f ? 1.f : 0.f;
     row_stats[b * 3 + 2] = ok && gt < 5.f ? 1.f : 0.f;
   }
@@ -794,9 +831,20 @@ extern "C" int vit_gemm_f32(int64_t M, int64_t N, int64_t K, const float* A, int
 extern "C" int vit_cross_entropy(const float* logits, const int64_t* labels, int64_t B, int64_t C, float* dlogits,
                                  float grad_scale, float* row_stats, vit_stream_t stream) {
   VIT_CHECK_ARG(logits && labels && B > 0 && C > 0, "vit_cross_entropy: bad args");
-  hipLaunchKernelGGL(ce_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, labels, (int)C, dlogits,
-                     grad_scale, row_stats);
+  hipLaunchKernelGGL(ce_kernel<false>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, labels,
+                     (const int64_t*)nullptr, (const float*)nullptr, 0.f, (int)C, dlogits, grad_scale, row_stats);
   VIT_LAUNCH_CHECK("vit_cross_entropy");
+}
+
+extern "C" int vit_cross_entropy_soft(const float* logits, const int64_t* labels, const int64_t* labels2,
+                                      const float* lam, float smoothing, int64_t B, int64_t C, float* dlogits,
+                                      float grad_scale, float* row_stats, vit_stream_t stream) {
+  VIT_CHECK_ARG(logits && labels && B > 0 && C > 0, "vit_cross_entropy_soft: bad args");
+  VIT_CHECK_ARG(smoothing >= 0.f && smoothing < 1.f, "vit_cross_entropy_soft: smoothing %g outside [0, 1)",
+                (double)smoothing);
+  hipLaunchKernelGGL(ce_kernel<true>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, labels, labels2,
+                     lam, smoothing, (int)C, dlogits, grad_scale, row_stats);
+  VIT_LAUNCH_CHECK("vit_cross_entropy_soft");
 }
 
 extern "C" int vit_sgd_step_dev(float* p, const float* g, float* buf, void* p_bf16, int64_t n, const float* hyper,

@@ -308,6 +308,11 @@ PrepArgs make_args(const uint8_t* images, int64_t B, int64_t H, int64_t W, int64
 //   anything larger          one thread per output pixel. The column's horizontal weights are computed once per
 //                            block into the LDS the band does not need here (up to kBandMax taps, a ratio of
 //                            66; above that they are recomputed per use - the same expression, the same bits).
+// vit_preprocess_u8_ragged_crop adds crops[b] = (top, left, h, w), torchvision's resized_crop (RandomResizedCrop, the
+// Inception crop): Pillow's crop(box).resize(size) is this resize run on the sub-rectangle, so the block builds both
+// axes - and chooses its path - from the box's (h, w), starts (top * W + left) * 3 bytes into the image and keeps the
+// whole image's row pitch 3 * W. A box that is empty or leaves the image is refused like a bad table row. One kernel:
+// without crops the box is the image.
 struct RaggedArgs {
   const uint8_t* bytes;
   long n_bytes;
@@ -321,14 +326,17 @@ struct RaggedArgs {
   float* out;
   const int64_t* labels_in;
   int64_t* labels_out;
+  const int64_t* crops;  // [B][4] = top, left, h, w of output b's crop box, or NULL = the whole image
 };
 
 // ceil(support) * 2 + 1 of axis_ksize, on the device
 __device__ inline int axis_ksize_dev(const Axis& a) { return (int)ceil(a.support) * 2 + 1; }
 
+// img points at the first pixel the axes address (the image's, or its crop's); row_bytes is the pitch of the whole
+// image, which a crop keeps.
 template <int KMAX>
-__device__ inline void ragged_tiled(const RaggedArgs& p, const uint8_t* img, const Axis& ax, const Axis& ay, int b,
-                                    int y0, int rows, int (*s_ky)[9], int* s_ymin, int* s_ycnt,
+__device__ inline void ragged_tiled(const RaggedArgs& p, const uint8_t* img, long row_bytes, const Axis& ax,
+                                    const Axis& ay, int b, int y0, int rows, int (*s_ky)[9], int* s_ymin, int* s_ycnt,
                                     uint32_t (*s_h)[kColsPerBlock]) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.y * kColsPerBlock + threadIdx.x;
@@ -354,7 +362,6 @@ __device__ inline void ragged_tiled(const RaggedArgs& p, const uint8_t* img, con
   __syncthreads();
   const int band0 = s_ymin[0];
   const int nband = s_ymin[rows - 1] + s_ycnt[rows - 1] - band0;  // <= kBandMax: both axes have <= 9 taps
-  const long row_bytes = (long)ax.in_size * 3;
   if (live) {
     const uint8_t* src = img + (long)band0 * row_bytes + (long)xmin * 3;
     for (int r = threadIdx.y; r < nband; r += kRowLanes) {
@@ -393,8 +400,9 @@ __device__ inline void ragged_tiled(const RaggedArgs& p, const uint8_t* img, con
 }
 
 // the per-pixel body for a block whose image has more than 9 taps on an axis; ksx = the horizontal kernel size
-__device__ inline void ragged_pixel(const RaggedArgs& p, const uint8_t* img, const Axis& ax, const Axis& ay, int ksx,
-                                    int b, int y0, int rows, uint32_t (*s_h)[kColsPerBlock]) {
+__device__ inline void ragged_pixel(const RaggedArgs& p, const uint8_t* img, long row_bytes, const Axis& ax,
+                                    const Axis& ay, int ksx, int b, int y0, int rows,
+                                    uint32_t (*s_h)[kColsPerBlock]) {
 #pragma clang fp contract(off)
   const int x = blockIdx.x * kColsPerBlock + threadIdx.x;
   const bool live = x < p.ow;
@@ -409,7 +417,6 @@ __device__ inline void ragged_pixel(const RaggedArgs& p, const uint8_t* img, con
   }
   if (!live) return;
   const long plane = (long)p.oh * p.ow;
-  const long row_bytes = (long)ax.in_size * 3;
   float* o = p.out + (long)b * 3 * plane + x;
   for (int r = threadIdx.y; r < rows; r += kRowLanes) {
     int ymin, ycnt;
@@ -458,6 +465,16 @@ __global__ void __launch_bounds__(kColsPerBlock* kRowLanes) preprocess_ragged_ke
       ok = H > 0 && H < (1 << 15) && W > 0 && W < (1 << 15) && off >= 0 && 3 * H * W <= p.n_bytes &&
            off <= p.n_bytes - 3 * H * W;
     }
+    // the crop box of this output (torchvision's resized_crop): the resize below runs on the sub-rectangle
+    long top = 0, left = 0, ch = H, cw = W;
+    if (ok && p.crops) {
+      top = p.crops[bl * 4];
+      left = p.crops[bl * 4 + 1];
+      ch = p.crops[bl * 4 + 2];
+      cw = p.crops[bl * 4 + 3];
+      // each bound is checked against H, W < 2^15 before it enters a sum, so nothing overflows
+      ok = ch > 0 && cw > 0 && top >= 0 && left >= 0 && ch <= H && cw <= W && top <= H - ch && left <= W - cw;
+    }
     if (threadIdx.x == 0 && threadIdx.y == 0 && blockIdx.x == 0 && blockIdx.y == 0 && p.labels_in && p.labels_out)
       p.labels_out[b] = ok ? p.labels_in[srci] : -1;
     if (!ok) {  // never read through: NaN for this output alone
@@ -470,34 +487,37 @@ __global__ void __launch_bounds__(kColsPerBlock* kRowLanes) preprocess_ragged_ke
       }
       continue;
     }
-    const Axis ax = make_axis((int)W, p.ow), ay = make_axis((int)H, p.oh);
+    const Axis ax = make_axis((int)cw, p.ow), ay = make_axis((int)ch, p.oh);
     const int ksx = axis_ksize_dev(ax), ksy = axis_ksize_dev(ay);
     const int ks = ksx > ksy ? ksx : ksy;
-    const uint8_t* img = p.bytes + off;
+    const long row_bytes = W * 3;  // the whole image's pitch, also under a crop
+    const uint8_t* img = p.bytes + off + (top * W + left) * 3;
     if (ks <= 3)
-      ragged_tiled<3>(p, img, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
+      ragged_tiled<3>(p, img, row_bytes, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
     else if (ks <= 5)
-      ragged_tiled<5>(p, img, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
+      ragged_tiled<5>(p, img, row_bytes, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
     else if (ks <= 9)
-      ragged_tiled<9>(p, img, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
+      ragged_tiled<9>(p, img, row_bytes, ax, ay, b, y0, rows, s_ky, s_ymin, s_ycnt, s_h);
     else
-      ragged_pixel(p, img, ax, ay, ksx, b, y0, rows, s_h);
+      ragged_pixel(p, img, row_bytes, ax, ay, ksx, b, y0, rows, s_h);
     __syncthreads();  // the next image of this block reuses the LDS
   }
 }
 
 }  // namespace
 
-extern "C" int vit_preprocess_u8_ragged(const uint8_t* bytes, int64_t n_bytes, const int64_t* geom, int64_t n_images,
-                                        const int64_t* index, int64_t B, const uint8_t* flips, int64_t out_h,
-                                        int64_t out_w, const float* mean_std, float* out, const int64_t* labels_in,
-                                        int64_t* labels_out, vit_stream_t stream) {
-  VIT_CHECK_ARG(bytes && geom && out && mean_std, "vit_preprocess_u8_ragged: null bytes / geom / out / mean_std");
+namespace {
+// the one launch behind vit_preprocess_u8_ragged (crops == NULL) and vit_preprocess_u8_ragged_crop
+int launch_ragged(const char* what, const uint8_t* bytes, int64_t n_bytes, const int64_t* geom, int64_t n_images,
+                  const int64_t* index, int64_t B, const uint8_t* flips, const int64_t* crops, int64_t out_h,
+                  int64_t out_w, const float* mean_std, float* out, const int64_t* labels_in, int64_t* labels_out,
+                  vit_stream_t stream) {
+  VIT_CHECK_ARG(bytes && geom && out && mean_std, "%s: null bytes / geom / out / mean_std", what);
   VIT_CHECK_ARG(B > 0 && n_images > 0 && n_bytes > 0 && out_h > 0 && out_w > 0,
-                "vit_preprocess_u8_ragged: B, n_images, n_bytes and the output size must be positive");
+                "%s: B, n_images, n_bytes and the output size must be positive", what);
   VIT_CHECK_ARG(out_h < (1 << 15) && out_w < (1 << 15) && B < (1LL << 31) && B * out_h * out_w < (1LL << 40) &&
                     n_images < (1LL << 40),
-                "vit_preprocess_u8_ragged: sizes too large");
+                "%s: sizes too large", what);
   RaggedArgs p;
   p.bytes = bytes;
   p.n_bytes = n_bytes;
@@ -515,12 +535,31 @@ extern "C" int vit_preprocess_u8_ragged(const uint8_t* bytes, int64_t n_bytes, c
   p.out = out;
   p.labels_in = labels_in;
   p.labels_out = labels_out;
+  p.crops = crops;
   const long cb = (out_w + kColsPerBlock - 1) / kColsPerBlock, rb = (out_h + kRowsPerBlock - 1) / kRowsPerBlock;
   // at most 65535 in z and fewer than 2^32 threads in the grid: the kernel strides the batch over z
   const long z = std::max(1L, std::min({(long)B, 65535L, ((1L << 24) - 1) / (cb * rb)}));
   hipLaunchKernelGGL(preprocess_ragged_kernel, dim3((unsigned)cb, (unsigned)rb, (unsigned)z),
                      dim3(kColsPerBlock, kRowLanes), 0, (hipStream_t)stream, p);
-  VIT_LAUNCH_CHECK("vit_preprocess_u8_ragged");
+  VIT_LAUNCH_CHECK(what);
+}
+}  // namespace
+
+extern "C" int vit_preprocess_u8_ragged(const uint8_t* bytes, int64_t n_bytes, const int64_t* geom, int64_t n_images,
+                                        const int64_t* index, int64_t B, const uint8_t* flips, int64_t out_h,
+                                        int64_t out_w, const float* mean_std, float* out, const int64_t* labels_in,
+                                        int64_t* labels_out, vit_stream_t stream) {
+  return launch_ragged("vit_preprocess_u8_ragged", bytes, n_bytes, geom, n_images, index, B, flips, nullptr, out_h,
+                       out_w, mean_std, out, labels_in, labels_out, stream);
+}
+
+extern "C" int vit_preprocess_u8_ragged_crop(const uint8_t* bytes, int64_t n_bytes, const int64_t* geom,
+                                             int64_t n_images, const int64_t* index, int64_t B, const uint8_t* flips,
+                                             const int64_t* crops, int64_t out_h, int64_t out_w,
+                                             const float* mean_std, float* out, const int64_t* labels_in,
+                                             int64_t* labels_out, vit_stream_t stream) {
+  return launch_ragged("vit_preprocess_u8_ragged_crop", bytes, n_bytes, geom, n_images, index, B, flips, crops, out_h,
+                       out_w, mean_std, out, labels_in, labels_out, stream);
 }
 
 extern "C" int vit_preprocess_u8(const uint8_t* images, int64_t B, int64_t H, int64_t W, int64_t image_stride,

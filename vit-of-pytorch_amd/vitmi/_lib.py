@@ -17,7 +17,7 @@ c_i32 = ctypes.c_int32
 c_f32 = ctypes.c_float
 c_vp = ctypes.c_void_p
 
-ABI_VERSION = 23  # vit_abi_version() of the library these prototypes describe
+ABI_VERSION = 24  # vit_abi_version() of the library these prototypes describe
 
 # enum vit_layout / vit_epilogue (include/vit_hip.h)
 K_CONTIG, MN_CONTIG = 0, 1
@@ -127,6 +127,9 @@ _SIGS = {
                                          c_vp, c_vp, c_vp, c_vp]),
     "vit_preprocess_u8_ragged": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
                                          c_vp, c_vp]),
+    "vit_preprocess_u8_ragged_crop": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp]),
+    "vit_mix_batch": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "vit_embed_grad": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(Dropout), c_vp]),
     "vit_embed_grad_accum": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(Dropout), c_i32,
                                      c_vp]),
@@ -136,6 +139,7 @@ _SIGS = {
     "vit_gemm_f32": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i32,
                              c_vp]),
     "vit_cross_entropy": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp]),
+    "vit_cross_entropy_soft": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp]),
     "vit_sgd_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "vit_cast_f32_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "vit_cast_pad_rows": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),

@@ -16,6 +16,12 @@ src/config.py:57-104). Additions for the MI355X path, all optional:
   --accum-steps K        (train) every optimizer step as K micro-batches of batch / (K * n_gpu) images, gradients
                          accumulated in the kernels; --batch-size stays the batch of one optimizer step
   --clip-grad-norm X     (train) clip the step's gradient to global 2-norm X (0: off)
+  --random-resized-crop  (train, ImageNet / TinyImageNet) torchvision's RandomResizedCrop in place of Resize, inside the
+                         ragged transform launch; --crop-scale LO HI (0.08 1.0) and --crop-ratio LO HI (0.75 1.3333)
+  --label-smoothing E    (train) cross entropy against (1-E) target + E/C; validation stays plain
+  --mixup-alpha A, --cutmix-alpha A   (train) Mixup / CutMix per batch, lambda ~ Beta(A, A) (vitmi.augment.BatchMixer);
+                         --mix-prob P (1.0) mixes a batch with probability P, --mix-switch-prob S (0.5) picks CutMix
+                         with probability S when both alphas are set
 
 Without --synthetic, the reference's own commands run on CIFAR read from disk (vitmi.datasets, vitmi.data):
     python -m vitmi.train --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path w.pth ...
@@ -136,8 +142,10 @@ def get_train_config(argv=None):
                              "batch of one optimizer step")
     parser.add_argument("--clip-grad-norm", type=float, default=0.0,
                         help="clip the gradient to this global 2-norm before each update (0: off)")
+    add_augment_args(parser, mixing=True)
     config = parser.parse_args(argv)
     _check_image_size(config)
+    check_augment_args(config)
     if config.accum_steps < 1 or config.batch_size % (config.accum_steps * max(1, config.n_gpu)):
         raise SystemExit(f"--batch-size {config.batch_size} is the batch of one optimizer step and must divide evenly "
                          f"into --accum-steps {config.accum_steps} micro-batches on each of {config.n_gpu} GPUs")
@@ -145,6 +153,52 @@ def get_train_config(argv=None):
     process_config(config)
     print_config(config)
     return config
+
+
+def add_augment_args(parser, mixing):
+    """the from-scratch augmentation flags, all off by default; mixing: also label smoothing and Mixup / CutMix"""
+    parser.add_argument("--random-resized-crop", default=False, action="store_true",
+                        help="ImageNet / TinyImageNet training: RandomResizedCrop in place of Resize")
+    parser.add_argument("--crop-scale", type=float, nargs=2, default=[0.08, 1.0], metavar=("LO", "HI"),
+                        help="--random-resized-crop: the crop's share of the image's area")
+    parser.add_argument("--crop-ratio", type=float, nargs=2, default=[3.0 / 4.0, 4.0 / 3.0], metavar=("LO", "HI"),
+                        help="--random-resized-crop: the crop's aspect ratio w / h")
+    if not mixing:
+        return
+    parser.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing of the training loss")
+    parser.add_argument("--mixup-alpha", type=float, default=0.0, help="Mixup: lambda ~ Beta(a, a) per batch (0: off)")
+    parser.add_argument("--cutmix-alpha", type=float, default=0.0,
+                        help="CutMix: lambda ~ Beta(a, a) per batch (0: off)")
+    parser.add_argument("--mix-prob", type=float, default=1.0, help="probability that a batch is mixed")
+    parser.add_argument("--mix-switch-prob", type=float, default=0.5,
+                        help="probability of CutMix over Mixup when both alphas are set")
+
+
+def check_augment_args(config):
+    """out-of-range augmentation flags, and the crop on a dataset whose transform has none, exit with one line"""
+    import math
+    lo, hi = config.crop_scale
+    if not (0.0 < lo <= hi <= 1.0):
+        raise SystemExit(f"--crop-scale {lo:g} {hi:g}: expected 0 < LO <= HI <= 1")
+    lo, hi = config.crop_ratio
+    if not (0.0 < lo <= hi and math.isfinite(hi)):
+        raise SystemExit(f"--crop-ratio {lo:g} {hi:g}: expected 0 < LO <= HI")
+    if config.random_resized_crop:
+        from .data import CROP_NEEDS_FOLDERS, FOLDER_DATASETS
+        if config.synthetic:
+            raise SystemExit("--random-resized-crop crops decoded image files: it does not go with --synthetic")
+        if config.dataset not in FOLDER_DATASETS:
+            raise SystemExit(CROP_NEEDS_FOLDERS.format(config.dataset))
+    if not hasattr(config, "label_smoothing"):
+        return
+    if not 0.0 <= config.label_smoothing < 1.0:
+        raise SystemExit(f"--label-smoothing {config.label_smoothing:g}: expected a value in [0, 1)")
+    for flag, v in (("--mixup-alpha", config.mixup_alpha), ("--cutmix-alpha", config.cutmix_alpha)):
+        if not (0.0 <= v and math.isfinite(v)):
+            raise SystemExit(f"{flag} {v:g}: expected a value >= 0")
+    for flag, v in (("--mix-prob", config.mix_prob), ("--mix-switch-prob", config.mix_switch_prob)):
+        if not 0.0 <= v <= 1.0:
+            raise SystemExit(f"{flag} {v:g}: expected a value in [0, 1]")
 
 
 def _check_image_size(config):

@@ -13,7 +13,9 @@ Real datasets (vitmi.datasets): CIFAR-10/100 parsed from disk go through Residen
 in HBM as stored (planar uint8), the sample order is the reference's seeded DataLoader order
 (epoch_order), and each step's batch is one vit_preprocess_u8_gather launch. ImageNet / TinyImageNet image
 folders go through FolderLoader: files decoded on the host by Pillow, of whatever sizes, packed end to end, and
-each step's batch is one vit_preprocess_u8_ragged launch, streamed or resident. `loaders` picks by --dataset.
+each step's batch is one vit_preprocess_u8_ragged launch, streamed or resident; with crop=(scale, ratio) the training
+split takes torchvision's RandomResizedCrop in the same launch (vit_preprocess_u8_ragged_crop, boxes from
+vitmi.augment.CropPlan). `loaders` picks by --dataset.
 """
 from __future__ import annotations
 
@@ -187,8 +189,8 @@ class _Slot:
 
     def __init__(self, batch_size, device):
         self.device = device
-        self.host_meta = torch.empty(batch_size * 4, dtype=torch.int64).pin_memory()
-        self.dev_meta = torch.empty(batch_size * 4, dtype=torch.int64, device=device)
+        self.host_meta = torch.empty(batch_size * 8, dtype=torch.int64).pin_memory()  # + the crop boxes
+        self.dev_meta = torch.empty(batch_size * 8, dtype=torch.int64, device=device)
         self.host_bytes = self.dev_bytes = None
         self.copied = torch.cuda.Event()  # the upload of this slot's batch, on the side stream
         self.consumed = None  # recorded by the consumer behind the launch that read the slot
@@ -232,14 +234,28 @@ class FolderLoader:
     resident=True  one decode pass packs the whole split into HBM with its table and labels (refused above
         `resident_gb`); then a batch is one launch with index = order[s:e], with no host work per step.
 
+    crop=(scale, ratio)  (training split only; ignored for eval) torchvision's RandomResizedCrop(size, scale, ratio) in
+        place of Resize: every sample of the epoch gets a box from vitmi.augment.CropPlan, a function of (seed, epoch,
+        position in the epoch's order) alone, and the launch is vit_preprocess_u8_ragged_crop. Whole images are still
+        packed: one path. Resident: the epoch's boxes are computed from the kept sizes and uploaded once with the
+        order and the flips. Streaming: the producer computes each batch's boxes after the decode and ships them in
+        the slot's table. `last_crops` holds the epoch's boxes by position (resident) or the last yielded batch's
+        (streaming): int64 [., 4] = (top, left, h, w) on the host, None without crop.
+
     `data_wait_s` is the time the last (or running) epoch's consumer spent waiting for the producer.
     `batch_size` is this rank's batch. Yields (float32 [b, 3, h, w], int64 [b]) on the device."""
 
     def __init__(self, paths, labels, batch_size, image_size, device, train=True, seed=42, world=1, rank=0,
                  num_classes=None, workers=8, resident=False, resident_gb=32.0, decode=None, depth=2,
-                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)):
+                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), crop=None):
         from . import datasets
         self.paths = list(paths)
+        self.crop_plan = None
+        if crop is not None and train:
+            from .augment import CropPlan
+            self.crop_plan = CropPlan(seed, crop[0], crop[1])
+        self.epoch = 0  # epochs started: the crop draws' second key
+        self.last_crops = self.crops = None
         labels = torch.as_tensor(labels).reshape(-1)
         if labels.numel() != len(self.paths):
             raise ValueError(f"FolderLoader: {len(self.paths)} paths but {labels.numel()} labels")
@@ -295,6 +311,7 @@ class FolderLoader:
             self.bytes[pos:pos + c.size].copy_(torch.from_numpy(c))
             pos += c.size
         self.geom = torch.from_numpy(geom).to(self.device)
+        self.host_geom = geom
         self.labels = self.host_labels.to(self.device)
 
     def _iter_resident(self):
@@ -302,19 +319,24 @@ class FolderLoader:
         for s, e in self.plan.slices():
             out = torch.empty(e - s, 3, h, w, device=self.device, dtype=torch.float32)
             target = torch.empty(e - s, device=self.device, dtype=torch.int64)
-            ops.preprocess_u8_ragged(self.bytes, self.geom, out, index=self.order[s:e],
-                                     flips=None if self.flips is None else self.flips[s:e], mean=self.mean,
-                                     std=self.std, labels_in=self.labels, labels_out=target)
+            flips = None if self.flips is None else self.flips[s:e]
+            if self.crops is None:
+                ops.preprocess_u8_ragged(self.bytes, self.geom, out, index=self.order[s:e], flips=flips,
+                                         mean=self.mean, std=self.std, labels_in=self.labels, labels_out=target)
+            else:
+                ops.preprocess_u8_ragged_crop(self.bytes, self.geom, out, self.crops[s:e], index=self.order[s:e],
+                                              flips=flips, mean=self.mean, std=self.std, labels_in=self.labels,
+                                              labels_out=target)
             yield out, target
 
     # -- streaming -----------------------------------------------------------------------------------------
-    def _produce(self, order, slices, pool, free, ready, stop, stream):
+    def _produce(self, order, slices, pool, free, ready, stop, stream, epoch):
         """the producer thread: decode ahead, pack, upload; hands (slot, count, bytes) or an exception to `ready`"""
         from collections import deque
         try:
             torch.cuda.set_device(self.device)
             pending, nxt = deque(), 0
-            for _ in slices:
+            for start, _ in slices:
                 while nxt < len(slices) and len(pending) <= self.depth:  # decode up to depth batches ahead
                     s, e = slices[nxt]
                     idx = order[s:e].tolist()
@@ -335,9 +357,12 @@ class FolderLoader:
                     meta[3 * k:3 * k + 3] = (pos, a.shape[0], a.shape[1])
                     pos += a.size
                 meta[3 * b:4 * b] = self.host_labels[idx].numpy()
+                if self.crop_plan is not None:
+                    meta[4 * b:8 * b] = self.crop_plan.boxes(epoch, start, [a.shape[0] for a in images],
+                                                             [a.shape[1] for a in images]).reshape(-1)
                 with torch.cuda.stream(stream):
                     slot.dev_bytes[:n_bytes].copy_(slot.host_bytes[:n_bytes], non_blocking=True)
-                    slot.dev_meta[:4 * b].copy_(slot.host_meta[:4 * b], non_blocking=True)
+                    slot.dev_meta[:8 * b].copy_(slot.host_meta[:8 * b], non_blocking=True)
                     slot.copied.record(stream)
                 ready.put((slot, b, n_bytes))
         except BaseException as e:  # surfaces in the consuming loop
@@ -356,7 +381,8 @@ class FolderLoader:
             free.put(_Slot(bmax, self.device))
         pool = ThreadPoolExecutor(self.workers, thread_name_prefix="vitmi-decode")
         stream = torch.cuda.Stream(self.device)
-        producer = threading.Thread(target=self._produce, args=(order, slices, pool, free, ready, stop, stream),
+        producer = threading.Thread(target=self._produce,
+                                    args=(order, slices, pool, free, ready, stop, stream, self.epoch),
                                     name="vitmi-producer", daemon=True)
         producer.start()
         try:
@@ -371,10 +397,17 @@ class FolderLoader:
                 target = torch.empty(b, device=self.device, dtype=torch.int64)
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(slot.copied)
-                ops.preprocess_u8_ragged(slot.dev_bytes, slot.dev_meta[:3 * b].view(b, 3), out,
-                                         flips=None if self.flips is None else self.flips[s:e], mean=self.mean,
-                                         std=self.std, labels_in=slot.dev_meta[3 * b:4 * b], labels_out=target,
-                                         n_bytes=n_bytes)
+                flips = None if self.flips is None else self.flips[s:e]
+                if self.crop_plan is None:
+                    ops.preprocess_u8_ragged(slot.dev_bytes, slot.dev_meta[:3 * b].view(b, 3), out, flips=flips,
+                                             mean=self.mean, std=self.std, labels_in=slot.dev_meta[3 * b:4 * b],
+                                             labels_out=target, n_bytes=n_bytes)
+                else:
+                    ops.preprocess_u8_ragged_crop(slot.dev_bytes, slot.dev_meta[:3 * b].view(b, 3), out,
+                                                  slot.dev_meta[4 * b:8 * b].view(b, 4), flips=flips, mean=self.mean,
+                                                  std=self.std, labels_in=slot.dev_meta[3 * b:4 * b],
+                                                  labels_out=target, n_bytes=n_bytes)
+                    self.last_crops = slot.host_meta[4 * b:8 * b].view(b, 4).clone()
                 slot.dev_bytes.record_stream(cur)
                 slot.dev_meta.record_stream(cur)
                 slot.consumed = torch.cuda.Event()
@@ -394,17 +427,31 @@ class FolderLoader:
             self.host_order = order
             self.order = order.to(self.device)
             self.flips = None if flips is None else flips.to(self.device)
+            self.epoch += 1
+            if self.crop_plan is not None and self.resident:
+                sizes = self.host_geom[order.numpy()]
+                self.last_crops = torch.from_numpy(self.crop_plan.boxes(self.epoch, 0, sizes[:, 1], sizes[:, 2]))
+                self.crops = self.last_crops.to(self.device)
         self.data_wait_s = 0.0
         return self._iter_resident() if self.resident else self._iter_streaming(self.host_order)
 
 
 FOLDER_DATASETS = ("ImageNet", "TinyImageNet")
+CROP_NEEDS_FOLDERS = ("--random-resized-crop runs inside the ragged image-folder transform (ImageNet, TinyImageNet); "
+                      "--dataset {} goes through the fixed-size gather transform, which has no crop")
 ON_DISK_FORMS = (
     "CIFAR10 and CIFAR100 in their published python or binary form (<data-dir>/CIFAR10/cifar-10-batches-py or "
     "cifar-10-batches-bin, <data-dir>/CIFAR100/cifar-100-python or cifar-100-binary); ImageNet as image folders "
     "(<data-dir>/ImageNet/train/<class>/<image files> and <data-dir>/ImageNet/val/<class>/<image files>); "
     "TinyImageNet as <data-dir>/TinyImageNet/train/<class>/images/<image files> with val/ in the same form or as "
     "the published val/images/ + val/val_annotations.txt")
+
+
+def crop_of(config):
+    """(scale, ratio) of --random-resized-crop, or None"""
+    if not getattr(config, "random_resized_crop", False):
+        return None
+    return tuple(config.crop_scale), tuple(config.crop_ratio)
 
 
 def folder_loaders(config, batch_size, device, world=1, rank=0, splits=("train", "test")):
@@ -431,7 +478,8 @@ def folder_loaders(config, batch_size, device, world=1, rank=0, splits=("train",
             loaders_.append(FolderLoader(paths, labels, batch_size, image_hw(config.image_size), device,
                                          train=split == "train", seed=config.seed, world=world, rank=rank,
                                          num_classes=config.num_classes, workers=getattr(config, "num_workers", 8),
-                                         resident=resident, resident_gb=getattr(config, "resident_gb", 32.0)))
+                                         resident=resident, resident_gb=getattr(config, "resident_gb", 32.0),
+                                         crop=crop_of(config)))
         except (datasets.DatasetError, ValueError) as e:
             raise SystemExit(f"{config.dataset} {sub} split: {e}") from e
     return loaders_
@@ -443,6 +491,8 @@ def loaders(config, batch_size, device, world=1, rank=0, splits=("train", "test"
     exits with the list of what is read."""
     if config.dataset in FOLDER_DATASETS:
         return folder_loaders(config, batch_size, device, world, rank, splits)
+    if getattr(config, "random_resized_crop", False):
+        raise SystemExit(CROP_NEEDS_FOLDERS.format(config.dataset))
     return cifar_loaders(config, batch_size, device, world, rank, splits)
 
 

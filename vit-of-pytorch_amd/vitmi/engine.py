@@ -667,12 +667,22 @@ class ViTEngine:
         return logits
 
     # ---- loss ------------------------------------------------------------------------------------
-    def cross_entropy(self, labels: torch.Tensor, grad_scale: float | None = None):
+    def cross_entropy(self, labels: torch.Tensor, grad_scale: float | None = None, labels2=None, lam=None,
+                      smoothing: float = 0.0):
         """Fused CE on the last logits: fills dlogits (scaled by grad_scale, default 1/b) and
-        per-row {loss, top1, top5}. Returns (dlogits, row_stats)."""
+        per-row {loss, top1, top5}. Returns (dlogits, row_stats). labels2 / lam (a Mixup / CutMix batch's second
+        labels int64 [b] and weights f32 [b]) or smoothing > 0 run the soft entry of the kernel
+        (vit_cross_entropy_soft); with all three off it is the plain entry, today's step."""
         a = self.acts(self._last_b)
         gs = 1.0 / a.b if grad_scale is None else grad_scale
-        ops.cross_entropy(a.logits, labels.to(self.dev, torch.int64).contiguous(), a.dlogits, gs, a.row_stats)
+        labels = labels.to(self.dev, torch.int64).contiguous()
+        if labels2 is None and lam is None and smoothing == 0.0:
+            ops.cross_entropy(a.logits, labels, a.dlogits, gs, a.row_stats)
+        else:
+            ops.cross_entropy_soft(a.logits, labels, a.dlogits, gs, a.row_stats,
+                                   labels2=None if labels2 is None else labels2.to(self.dev, torch.int64).contiguous(),
+                                   lam=None if lam is None else lam.to(self.dev, torch.float32).contiguous(),
+                                   smoothing=smoothing)
         return a.dlogits, a.row_stats
 
     # ---- backward --------------------------------------------------------------------------------

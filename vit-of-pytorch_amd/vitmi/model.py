@@ -344,31 +344,50 @@ class VisionTransformer(nn.Module):
 class CrossEntropyLoss(nn.Module):
     """nn.CrossEntropyLoss() (mean) on the HIP cross-entropy kernel (reference src/train.py:151).
     The kernel also counts top-1 / top-5 hits per row (src/utils.py:28-41): `last_row_stats`
-    holds {loss, top1, top5} [b, 3] of the latest call, which vitmi.train uses for accuracy."""
+    holds {loss, top1, top5} [b, 3] of the latest call, which vitmi.train uses for accuracy.
+    label_smoothing > 0 (nn.CrossEntropyLoss(label_smoothing=eps)) or a vitmi.augment.MixedTarget (a Mixup / CutMix
+    batch: labels y and y2 weighted lam and 1 - lam, timm's SoftTargetCrossEntropy on mixup_target) runs the soft
+    entry of the same kernel; hits are then counted against y, the samples' own labels. An int64 target with
+    label_smoothing == 0 is the plain kernel, as ever."""
 
-    def __init__(self):
+    def __init__(self, label_smoothing=0.0):
         super().__init__()
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"CrossEntropyLoss: label_smoothing {label_smoothing} outside [0, 1)")
+        self.label_smoothing = float(label_smoothing)
         self.last_row_stats = None
 
     def forward(self, logits, target):
+        from .augment import MixedTarget
         st = torch.empty(logits.shape[0], 3, device=logits.device)
-        loss = _CEFunction.apply(logits, target, st)
+        if isinstance(target, MixedTarget):
+            loss = _CEFunction.apply(logits, target.y, st, target.y2, target.lam, self.label_smoothing)
+        elif self.label_smoothing > 0:
+            loss = _CEFunction.apply(logits, target, st, None, None, self.label_smoothing)
+        else:
+            loss = _CEFunction.apply(logits, target, st)
         self.last_row_stats = st
         return loss
 
 
 class _CEFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, st):
+    def forward(ctx, logits, target, st, target2=None, lam=None, smoothing=0.0):
         from . import ops
         logits = logits.float().contiguous()
         b, c = logits.shape
         dl = torch.empty_like(logits)
-        ops.cross_entropy(logits, target.to(torch.int64).contiguous(), dl, 1.0 / b, st)
+        target = target.to(torch.int64).contiguous()
+        if target2 is None and lam is None and smoothing == 0.0:
+            ops.cross_entropy(logits, target, dl, 1.0 / b, st)
+        else:
+            ops.cross_entropy_soft(logits, target, dl, 1.0 / b, st,
+                                   labels2=None if target2 is None else target2.to(torch.int64).contiguous(),
+                                   lam=None if lam is None else lam.float().contiguous(), smoothing=smoothing)
         ctx.save_for_backward(dl)
         return st[:, 0].mean()
 
     @staticmethod
     def backward(ctx, g):
         dl, = ctx.saved_tensors
-        return dl * g, None, None
+        return dl * g, None, None, None, None, None

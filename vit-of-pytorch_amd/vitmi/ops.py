@@ -281,6 +281,26 @@ def preprocess_u8_ragged(bytes, geom, out, index=None, flips=None, mean=(0.5, 0.
     index int64 [B], flips uint8 [B] (by output image), out f32 [B, 3, h, w]; labels_out[b] = labels_in[index[b]]
     when both are given (int64 [n] / [B]). A bad index or a table row that does not fit `n_bytes` gives a NaN
     image and label -1 for that output alone; the library refuses null pointers and empty or oversized batches."""
+    _preprocess_ragged("preprocess_u8_ragged", bytes, geom, out, index, flips, None, mean, std, labels_in, labels_out,
+                       n_bytes)
+
+
+def preprocess_u8_ragged_crop(bytes, geom, out, crops, index=None, flips=None, mean=(0.5, 0.5, 0.5),
+                              std=(0.5, 0.5, 0.5), labels_in=None, labels_out=None, n_bytes=None):
+    """preprocess_u8_ragged of a crop box per output (vit_preprocess_u8_ragged_crop): crops int64 [B, 4] on the
+    device, row b = (top, left, h, w) of output b's box in source image index[b]; out[b] is Pillow's
+    crop(...).resize(...) of it, bit for bit, then flip and normalisation. crops None: the whole images. A box that
+    leaves its image, or an empty one, gives a NaN image and label -1 for that output alone."""
+    _chk(crops, torch.int64, "crops")
+    if crops is not None and (crops.dim() != 2 or tuple(crops.shape) != (out.shape[0], 4) or
+                              not crops.is_contiguous()):
+        raise ValueError(f"preprocess_u8_ragged_crop: crops int64 [B, 4], contiguous, got {tuple(crops.shape)}")
+    _preprocess_ragged("preprocess_u8_ragged_crop", bytes, geom, out, index, flips, crops, mean, std, labels_in,
+                       labels_out, n_bytes)
+
+
+def _preprocess_ragged(what, bytes, geom, out, index, flips, crops, mean, std, labels_in, labels_out, n_bytes):
+    """the checks and the call both ragged entries share; `what` names the public wrapper"""
     _chk(bytes, torch.uint8, "bytes")
     _chk(geom, torch.int64, "geom")
     _chk(out, F32, "out")
@@ -289,25 +309,51 @@ def preprocess_u8_ragged(bytes, geom, out, index=None, flips=None, mean=(0.5, 0.
     _chk(labels_in, torch.int64, "labels_in")
     _chk(labels_out, torch.int64, "labels_out")
     if bytes.dim() != 1 or geom.dim() != 2 or geom.shape[1] != 3 or out.dim() != 4 or out.shape[1] != 3:
-        raise ValueError(f"preprocess_u8_ragged: bytes [n_bytes], geom [n,3] -> out [B,3,h,w], got "
+        raise ValueError(f"{what}: bytes [n_bytes], geom [n,3] -> out [B,3,h,w], got "
                          f"{tuple(bytes.shape)}, {tuple(geom.shape)} -> {tuple(out.shape)}")
     n, B = geom.shape[0], out.shape[0]
     if (index is not None and (index.dim() != 1 or index.numel() != B)) or (index is None and B > n) or \
             (flips is not None and flips.numel() != B) or (labels_out is not None and labels_out.numel() != B) or \
             (labels_in is not None and labels_in.numel() != n):
-        raise ValueError("preprocess_u8_ragged: batch mismatch")
+        raise ValueError(f"{what}: batch mismatch")
     for name, t in (("bytes", bytes), ("geom", geom), ("out", out), ("index", index), ("flips", flips),
                     ("labels_in", labels_in), ("labels_out", labels_out)):
         if t is not None and not t.is_contiguous():
-            raise ValueError(f"preprocess_u8_ragged: {name} must be contiguous")
+            raise ValueError(f"{what}: {name} must be contiguous")
     if n_bytes is None:
         n_bytes = bytes.numel()
     if not 0 <= int(n_bytes) <= bytes.numel():
-        raise ValueError(f"preprocess_u8_ragged: n_bytes {n_bytes} outside [0, {bytes.numel()}]")
+        raise ValueError(f"{what}: n_bytes {n_bytes} outside [0, {bytes.numel()}]")
     ms = (ctypes.c_float * 6)(*[float(v) for v in mean], *[float(v) for v in std])
-    check(lib().vit_preprocess_u8_ragged(_p(bytes), int(n_bytes), _p(geom), n, _p(index), B, _p(flips), out.shape[2],
-                                         out.shape[3], ms, _p(out), _p(labels_in), _p(labels_out), _stream()),
-          "vit_preprocess_u8_ragged")
+    if what == "preprocess_u8_ragged":
+        check(lib().vit_preprocess_u8_ragged(_p(bytes), int(n_bytes), _p(geom), n, _p(index), B, _p(flips),
+                                             out.shape[2], out.shape[3], ms, _p(out), _p(labels_in), _p(labels_out),
+                                             _stream()), "vit_preprocess_u8_ragged")
+    else:
+        check(lib().vit_preprocess_u8_ragged_crop(_p(bytes), int(n_bytes), _p(geom), n, _p(index), B, _p(flips),
+                                                  _p(crops), out.shape[2], out.shape[3], ms, _p(out), _p(labels_in),
+                                                  _p(labels_out), _stream()), "vit_preprocess_u8_ragged_crop")
+
+
+def mix_batch(x, out, pair, lam, box):
+    """Mixup / CutMix of a finished batch in one pass (vit_mix_batch): x, out f32 [B, 3, H, W] on the device,
+    contiguous, not overlapping; pair int64 [B], lam f32 [B], box int64 [B, 4] = (y0, y1, x0, x1) half-open.
+    Inside sample b's box out = x[pair[b]] exactly, elsewhere lam[b] x[b] + (1 - lam[b]) x[pair[b]]; a pair entry
+    outside [0, B) gives a NaN sample."""
+    _chk(x, F32, "x")
+    _chk(out, F32, "out")
+    _chk(pair, torch.int64, "pair")
+    _chk(lam, F32, "lam")
+    _chk(box, torch.int64, "box")
+    if x.dim() != 4 or x.shape[1] != 3 or out.shape != x.shape:
+        raise ValueError(f"mix_batch: x and out f32 [B, 3, H, W], got {tuple(x.shape)} -> {tuple(out.shape)}")
+    B, _, H, W = x.shape
+    if pair.numel() != B or lam.numel() != B or tuple(box.shape) != (B, 4):
+        raise ValueError("mix_batch: pair [B], lam [B], box [B, 4]")
+    for name, t in (("x", x), ("out", out), ("pair", pair), ("lam", lam), ("box", box)):
+        if not t.is_contiguous():
+            raise ValueError(f"mix_batch: {name} must be contiguous")
+    check(lib().vit_mix_batch(_p(x), _p(out), B, H, W, _p(pair), _p(lam), _p(box), _stream()), "vit_mix_batch")
 
 
 def embed_grad(dh0, B, N, D, dpos, dcls, dconv_bias, dropout=None, accumulate=False):
@@ -352,6 +398,24 @@ def cross_entropy(logits, labels, dlogits, grad_scale, row_stats):
     B, C = logits.shape
     check(lib().vit_cross_entropy(_p(logits), _p(labels), B, C, _p(dlogits), grad_scale, _p(row_stats), _stream()),
           "vit_cross_entropy")
+
+
+def cross_entropy_soft(logits, labels, dlogits, grad_scale, row_stats, labels2=None, lam=None, smoothing=0.0):
+    """vit_cross_entropy_soft: cross entropy against t = (1-eps)(lam onehot(labels) + (1-lam) onehot(labels2)) +
+    eps/C. labels2 int64 [B] (None: labels), lam f32 [B] (None: 1), smoothing eps in [0, 1). Hits in row_stats are
+    counted against `labels`. With both None and eps = 0 the outputs are cross_entropy's, bit for bit."""
+    _chk(logits, F32, "logits")
+    _chk(labels, torch.int64, "labels")
+    _chk(labels2, torch.int64, "labels2")
+    _chk(lam, F32, "lam")
+    B, C = logits.shape
+    for name, t in (("labels", labels), ("labels2", labels2), ("lam", lam)):
+        if t is not None and (t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"cross_entropy_soft: {name} must be contiguous with {B} elements")
+    if not 0.0 <= float(smoothing) < 1.0:
+        raise ValueError(f"cross_entropy_soft: smoothing {smoothing} outside [0, 1)")
+    check(lib().vit_cross_entropy_soft(_p(logits), _p(labels), _p(labels2), _p(lam), float(smoothing), B, C,
+                                       _p(dlogits), grad_scale, _p(row_stats), _stream()), "vit_cross_entropy_soft")
 
 
 def sgd_step(p, g, buf, p_bf16, n, lr, momentum, wd, first):

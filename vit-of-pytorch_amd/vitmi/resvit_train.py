@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from . import resvit
 from .optim import AdamW, clip_grad_norm_, get_cosine_schedule_with_warmup
-from .config import _check_image_size, _image_size, image_hw, process_config
+from .config import _check_image_size, _image_size, add_augment_args, check_augment_args, image_hw, process_config
 from .flat import sinks as _flat_sinks
 from .train import MetricTracker, StepWriter, SyntheticDataLoader, _rank_mean, rank_batch, set_seed
 
@@ -321,8 +321,10 @@ def get_train_config(argv=None):
       help="image folders: decode the split once and keep it in HBM instead of streaming it")
     a("--resident-gb", type=float, default=32.0,
       help="image folders: the largest decoded split --resident-data may hold, in GB")
+    add_augment_args(p, mixing=False)  # --random-resized-crop (TinyImageNet / ImageNet); the distillation loss is as it was
     config = p.parse_args(argv)
     _check_image_size(config)
+    check_augment_args(config)
     config.num_classes = get_num_classes_for_dataset(config.dataset)
     return config
 

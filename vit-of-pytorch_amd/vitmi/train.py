@@ -34,6 +34,13 @@ save_model (:69-81), main (:84-194); MetricTracker / the step writer follow src/
     micro-batch weighted by its share of the group's samples. Validation also runs at the micro-batch size (the
     engine keeps a full activation set per batch size, so a full-size validation batch would undo the saving): the
     validation means are over micro-batches.
+  * from-scratch training (all off by default; with none given the step is launch for launch what it was):
+    `--random-resized-crop` (ImageNet / TinyImageNet: the Inception crop inside the ragged transform launch),
+    `--label-smoothing eps` (the soft entry of the cross-entropy kernel) and `--mixup-alpha` / `--cutmix-alpha`
+    (vitmi.augment.BatchMixer: one vit_mix_batch pass over each rank's micro-batch, after the loader and before the
+    forward). The mix is reproducible for a fixed configuration but not invariant across rank counts or
+    --accum-steps, since partners are drawn inside the micro-batch; the crop boxes are invariant. Validation always
+    uses plain cross entropy.
   * `--clip-grad-norm X` clips the accumulated (and, data parallel, reduced) gradient to global 2-norm X before the
     update (vitmi.optim.SGD(max_grad_norm=X)).
 """
@@ -242,7 +249,8 @@ def steps_in_epoch(data_loader, accum_steps=1):
     return -(-len(data_loader) // accum_steps)
 
 
-def _train_epoch_accum(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device, accum_steps):
+def _train_epoch_accum(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device, accum_steps,
+                       mixer=None):
     """train_epoch for accum_steps > 1: every optimizer step takes up to accum_steps micro-batches"""
     metrics.reset()
     steps = steps_in_epoch(data_loader, accum_steps)
@@ -257,6 +265,8 @@ def _train_epoch_accum(epoch, model, data_loader, criterion, optimizer, lr_sched
         for i, ((batch_data, batch_target), w) in enumerate(zip(group, weights)):
             batch_data = batch_data.to(device, non_blocking=True)
             batch_target = batch_target.to(device, non_blocking=True)
+            if mixer is not None:  # within this rank's micro-batch
+                batch_data, batch_target = mixer(batch_data, batch_target)
             # the gradients stay local until the step's last micro-batch (one all-reduce per optimizer step)
             with model.no_sync() if i + 1 < len(group) else contextlib.nullcontext():
                 batch_pred = model(batch_data)
@@ -283,16 +293,20 @@ def _train_epoch_accum(epoch, model, data_loader, criterion, optimizer, lr_sched
 
 
 def train_epoch(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device=torch.device("cpu"),
-                accum_steps=1):
+                accum_steps=1, mixer=None):
     """reference src/train.py:12-37 (one optimizer step per batch; accum_steps > 1: per accum_steps micro-batches of
-    the loader, their gradients accumulated and the metrics their sample-weighted means)."""
+    the loader, their gradients accumulated and the metrics their sample-weighted means). mixer (vitmi.augment.
+    BatchMixer): every batch is mixed after the loader and before the forward, and the criterion gets its
+    MixedTarget; the accuracies are then against the samples' own labels."""
     if accum_steps > 1:
         return _train_epoch_accum(epoch, model, data_loader, criterion, optimizer, lr_scheduler, metrics, device,
-                                  accum_steps)
+                                  accum_steps, mixer)
     metrics.reset()
     for batch_idx, (batch_data, batch_target) in enumerate(data_loader):
         batch_data = batch_data.to(device, non_blocking=True)
         batch_target = batch_target.to(device, non_blocking=True)
+        if mixer is not None:
+            batch_data, batch_target = mixer(batch_data, batch_target)
         optimizer.zero_grad()
         batch_pred = model(batch_data)
         loss = criterion(batch_pred, batch_target)
@@ -484,7 +498,15 @@ def main(argv=None):
                                            max(1, config.steps_per_epoch // 10), device,
                                            seed=10_000 + config.seed + rank)
 
-    criterion = CrossEntropyLoss()
+    # training: label smoothing and, under Mixup / CutMix, the mixed target; validation: always plain cross entropy,
+    # so that the validation loss stays comparable across runs
+    criterion = CrossEntropyLoss(label_smoothing=config.label_smoothing)
+    valid_criterion = CrossEntropyLoss()
+    mixer = None
+    if config.mixup_alpha > 0 or config.cutmix_alpha > 0:
+        from .augment import BatchMixer
+        mixer = BatchMixer(config.mixup_alpha, config.cutmix_alpha, config.mix_prob, config.mix_switch_prob,
+                           seed=config.seed + rank)
     optimizer = SGD(params=model.parameters(), lr=config.lr, weight_decay=config.wd, momentum=0.9, model=model,
                     max_grad_norm=config.clip_grad_norm if config.clip_grad_norm > 0 else None)
     lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer=optimizer, max_lr=config.lr,
@@ -503,9 +525,9 @@ def main(argv=None):
         log = {"epoch": epoch}
         model.train()
         log.update(train_epoch(epoch, model, train_loader, criterion, optimizer, lr_scheduler, train_metrics, device,
-                               accum_steps=config.accum_steps))
+                               accum_steps=config.accum_steps, mixer=mixer))
         model.eval()
-        result = valid_epoch(epoch, model, valid_loader, criterion, valid_metrics, device)
+        result = valid_epoch(epoch, model, valid_loader, valid_criterion, valid_metrics, device)
         log.update(**{"val_" + k: v for k, v in result.items()})
         best = log["val_acc1"] > best_acc
         if best:
