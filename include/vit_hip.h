@@ -601,6 +601,24 @@ int vit_adamw_update(float* p, float* g, float* m, float* v, void* p_bf16, const
                      const float* table, float decay, float beta1, float beta2, float one_minus_beta1,
                      float one_minus_beta2, float eps, int32_t write_grad, vit_stream_t stream);
 int vit_adamw_chunk_elems(void);
+/* The ViT engine's AdamW step over its whole flat buffer in one launch: decay groups, the weight EMA and the bf16
+ * mirror. chunks[3c..3c+2] = {flags, start element, length <= vit_adamw_chunk_elems()}; bit 0 of flags: the chunk's
+ * parameters are decayed (a clear bit: p is not multiplied at all); any other bit is refused. The chunk table is
+ * PAGE-LOCKED HOST memory (hipHostMalloc / a pinned torch tensor): it is checked here on the host (flags, start a
+ * multiple of 4, 1 <= length <= the chunk size) before anything is launched, and the kernel reads it through the
+ * allocation's device address. table is one float4 {step_size, sqrt(bc2), active, coef}: vit_adamw_prep's row for
+ * nseg = 1 (the engine gives every parameter a gradient every step, so one step count serves). Per element, in
+ * vit_adamw_update's order:
+ *   g *= coef; p *= decay if flagged; m += (1-beta1)(g - m); v = beta2 v + (1-beta2) g^2;
+ *   p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps)
+ * then ema += ema_one_minus_decay (p - ema) if ema != NULL; p_bf16 = bf16(p) (RNE) if p_bf16 != NULL; g is written
+ * back if write_grad. Alignment as vit_adamw_update: 16-byte buffers (ema too), 8-byte mirror. Alignment padding may
+ * ride in a chunk when it is zero in p, g, m, v and ema: the update keeps it zero.
+ * HBM work per element with everything on: 20 B read + 18 B written (+ 4 B with write_grad). */
+int vit_adamw_ema_update(float* p, float* g, float* m, float* v, void* p_bf16, float* ema, const int64_t* chunks,
+                         int32_t nchunks, const float* table, float decay, float beta1, float beta2,
+                         float one_minus_beta1, float one_minus_beta2, float eps, float ema_one_minus_decay,
+                         int32_t write_grad, vit_stream_t stream);
 /* g[i] *= *coef (device scalar; the in-place scaling of clip_grad_norm_) */
 int vit_scale_by_coef(float* g, int64_t n, const float* coef, vit_stream_t stream);
 /* bytes of device memory at ptr set to 0 on the stream (hipMemsetAsync) */

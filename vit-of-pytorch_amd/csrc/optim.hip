@@ -12,9 +12,14 @@
 //                       clip scale, decoupled weight decay, the two moments and the update, in
 //                       torch's single-tensor AdamW order (torch/optim/adamw.py _single_tensor_adam)
 //   vit_scale_by_coef   grads *= coef (device scalar): the standalone clip_grad_norm_
+//   vit_adamw_ema_update  the ViT engine's from-scratch step over its whole flat buffer: the same update with a decay
+//                       flag per chunk (timm's no-decay groups), the weight EMA and the bf16 mirror in the same pass;
+//                       one step count (vit_adamw_prep with nseg = 1), the chunk table checked on the host
 //
 // HBM work per element of the update: p, g, m, v read + p, m, v (+ g when the clipped gradient is
 // written back) written = 28-32 B; the norm pass reads g once (4 B).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -148,6 +153,118 @@ __global__ void __launch_bounds__(256) adamw_update_kernel(float* __restrict__ p
   }
 }
 
+// ---- the ViT engine's step: AdamW with decay groups, the weight EMA and the bf16 mirror in one pass ----------------
+// One workgroup per chunk {flags, start, length <= kChunk} of the engine's flat buffer; bit 0 of flags: the chunk's
+// parameters are decayed. The arithmetic is adamw_update_kernel's, line for line. The kernel is byte-bound (20 B read,
+// 18 B written per element with everything on), so every lane moves 16 B per access and issues the loads of two
+// float4 groups of all five arrays (10 x 16 B) ahead of the arithmetic (hipcc keeps 9 of them in front of the first
+// wait). At 96 VGPRs 5 workgroups of 4 waves fit a CU: about 180 KB of loads in flight per CU, several times the HBM
+// latency-bandwidth product. Measured (profiles/r11/adamw_ema_step.txt): 0.93 of the byte floor at 6.3 TB/s for the
+// ViT-B/16 buffer, 0.97 for ViT-H/14. The chunk table lives in page-locked host memory (the host checks it before the
+// launch); each workgroup reads its 24 bytes once, which the other resident workgroups hide.
+struct AdamwEmaConsts {
+  float decay, beta2, omb1, omb2, eps, omd, step_size, bc2s, coef;
+};
+
+template <bool kDecay, bool kEma>
+__device__ __forceinline__ void adamw_ema_elem(const AdamwEmaConsts& k, float& pp, float& gg, float& mm, float& vv,
+                                               float& ee) {
+  gg *= k.coef;
+  if (kDecay) pp *= k.decay;                            // an undecayed parameter is not multiplied at all
+  mm += k.omb1 * (gg - mm);
+  vv = vv * k.beta2 + k.omb2 * gg * gg;
+  const float denom = sqrtf(vv) / k.bc2s + k.eps;
+  pp -= k.step_size * (mm / denom);
+  if (kEma) ee += k.omd * (pp - ee);                    // ema.lerp_(p', 1 - ema_decay)
+}
+
+template <bool kDecay, bool kEma>
+__device__ __forceinline__ void adamw_ema_vec(const AdamwEmaConsts& k, float4& pv, float4& gv, float4& mv, float4& vv,
+                                              float4& ev) {
+  adamw_ema_elem<kDecay, kEma>(k, pv.x, gv.x, mv.x, vv.x, ev.x);
+  adamw_ema_elem<kDecay, kEma>(k, pv.y, gv.y, mv.y, vv.y, ev.y);
+  adamw_ema_elem<kDecay, kEma>(k, pv.z, gv.z, mv.z, vv.z, ev.z);
+  adamw_ema_elem<kDecay, kEma>(k, pv.w, gv.w, mv.w, vv.w, ev.w);
+}
+
+template <bool kDecay, bool kEma>
+__device__ __forceinline__ void adamw_ema_chunk(const AdamwEmaConsts& k, float* __restrict__ p, float* __restrict__ g,
+                                                float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ pb,
+                                                float* __restrict__ ema, long len, int write_grad) {
+  const long n4 = len / 4;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  float4* g4 = reinterpret_cast<float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  float4* e4 = reinterpret_cast<float4*>(ema);
+  uint2* b4 = reinterpret_cast<uint2*>(pb);
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto store = [&](long i, const float4& pv, const float4& gv, const float4& mv, const float4& vv, const float4& ev) {
+    p4[i] = pv;
+    m4[i] = mv;
+    v4[i] = vv;
+    if (kEma) e4[i] = ev;
+    if (write_grad) g4[i] = gv;
+    if (pb) {
+      uint2 u;
+      u.x = pack2bf(pv.x, pv.y);
+      u.y = pack2bf(pv.z, pv.w);
+      b4[i] = u;
+    }
+  };
+  for (long i = threadIdx.x; i < n4; i += 512) {
+    const bool two = i + 256 < n4;
+    const long j = two ? i + 256 : i;  // (a lane without a second group loads its first again: no branch around loads)
+    // every load of both groups first
+    float4 p0 = p4[i], g0 = g4[i], m0 = m4[i], v0 = v4[i], e0 = kEma ? e4[i] : zero;
+    float4 p1 = p4[j], g1 = g4[j], m1 = m4[j], v1 = v4[j], e1 = kEma ? e4[j] : zero;
+    __builtin_amdgcn_sched_barrier(0);  // keep the ten loads ahead of the arithmetic and the stores
+    adamw_ema_vec<kDecay, kEma>(k, p0, g0, m0, v0, e0);
+    store(i, p0, g0, m0, v0, e0);
+    if (two) {
+      adamw_ema_vec<kDecay, kEma>(k, p1, g1, m1, v1, e1);
+      store(j, p1, g1, m1, v1, e1);
+    }
+  }
+  const long tail = n4 * 4 + threadIdx.x;  // a parameter's last 1..3 elements
+  if (tail < len) {
+    float pp = p[tail], gg = g[tail], mm = m[tail], vv = v[tail], ee = kEma ? ema[tail] : 0.f;
+    adamw_ema_elem<kDecay, kEma>(k, pp, gg, mm, vv, ee);
+    p[tail] = pp;
+    m[tail] = mm;
+    v[tail] = vv;
+    if (kEma) ema[tail] = ee;
+    if (write_grad) g[tail] = gg;
+    if (pb) pb[tail] = f2bf(pp);
+  }
+}
+
+__global__ void __launch_bounds__(256) adamw_ema_update_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               bf16_t* __restrict__ pb, float* __restrict__ ema,
+                                                               const int64_t* __restrict__ chunks,
+                                                               const float4* __restrict__ table, float decay,
+                                                               float beta2, float omb1, float omb2, float eps, float omd,
+                                                               int write_grad) {
+  const int64_t flags = chunks[3 * blockIdx.x], start = chunks[3 * blockIdx.x + 1], len = chunks[3 * blockIdx.x + 2];
+  const float4 t = table[0];
+  if (t.z == 0.0f) return;  // (vit_adamw_prep's row of a parameter set without a gradient)
+  const AdamwEmaConsts k = {decay, beta2, omb1, omb2, eps, omd, t.x, t.y, t.w};
+  auto run = [&](auto decayed, auto with_ema) {
+    adamw_ema_chunk<decltype(decayed)::value, decltype(with_ema)::value>(k, p + start, g + start, m + start, v + start,
+                                                                        pb ? pb + start : nullptr,
+                                                                        ema ? ema + start : nullptr, (long)len,
+                                                                        write_grad);
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  if (flags & 1) {
+    if (ema) run(T{}, T{}); else run(T{}, F{});
+  } else {
+    if (ema) run(F{}, T{}); else run(F{}, F{});
+  }
+}
+
 __global__ void scale_by_coef_kernel(float* __restrict__ g, long n, const float* __restrict__ coef) {
   const float c = *coef;
   const long n4 = n / 4;
@@ -197,6 +314,38 @@ extern "C" int vit_adamw_update(float* p, float* g, float* m, float* v, void* p_
 }
 
 extern "C" int vit_adamw_chunk_elems(void) { return kChunk; }
+
+extern "C" int vit_adamw_ema_update(float* p, float* g, float* m, float* v, void* p_bf16, float* ema,
+                                    const int64_t* chunks, int32_t nchunks, const float* table, float decay,
+                                    float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                    float ema_one_minus_decay, int32_t write_grad, vit_stream_t stream) {
+  VIT_CHECK_ARG(p && g && m && v && chunks && table && nchunks >= 0, "vit_adamw_ema_update: bad args");
+  VIT_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0 &&
+                    (uintptr_t)p_bf16 % 8 == 0,
+                "vit_adamw_ema_update: buffers must be 16-B aligned (bf16 mirror 8-B)");
+  if (nchunks == 0) return VIT_OK;
+  // The chunk table is read here, on the host, before anything is launched, and by the kernel through the same
+  // allocation's device address: it has to be page-locked host memory.
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, chunks) != hipSuccess) {
+    (void)hipGetLastError();
+    attr.type = hipMemoryTypeUnregistered;
+  }
+  VIT_CHECK_ARG(attr.type == hipMemoryTypeHost && attr.devicePointer,
+                "vit_adamw_ema_update: the chunk table must be page-locked host memory (it is checked on the host)");
+  for (int32_t c = 0; c < nchunks; ++c) {
+    const int64_t flags = chunks[3 * c], start = chunks[3 * c + 1], len = chunks[3 * c + 2];
+    VIT_CHECK_ARG((flags & ~(int64_t)1) == 0, "vit_adamw_ema_update: chunk %d has flags 0x%llx (bit 0: decayed)", (int)c,
+                  (unsigned long long)flags);
+    VIT_CHECK_ARG(start >= 0 && start % 4 == 0 && len > 0 && len <= kChunk,
+                  "vit_adamw_ema_update: chunk %d starts at %lld with %lld elements (a multiple of 4; 1..%d)", (int)c,
+                  (long long)start, (long long)len, kChunk);
+  }
+  hipLaunchKernelGGL(adamw_ema_update_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     (bf16_t*)p_bf16, ema, (const int64_t*)attr.devicePointer, (const float4*)table, decay, beta2,
+                     one_minus_beta1, one_minus_beta2, eps, ema_one_minus_decay, (int)write_grad);
+  VIT_LAUNCH_CHECK("vit_adamw_ema_update");
+}
 
 extern "C" int vit_scale_by_coef(float* g, int64_t n, const float* coef, vit_stream_t stream) {
   VIT_CHECK_ARG(g && coef && n >= 0 && (uintptr_t)g % 16 == 0, "vit_scale_by_coef: bad args");

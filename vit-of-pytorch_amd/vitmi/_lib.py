@@ -166,6 +166,8 @@ _SIGS = {
     "vit_adamw_update": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32,
                                  c_f32, c_i32, c_vp]),
     "vit_adamw_chunk_elems": (c_i32, []),
+    "vit_adamw_ema_update": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32,
+                                     c_f32, c_f32, c_f32, c_i32, c_vp]),
     "vit_scale_by_coef": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "vit_zero": (c_i32, [c_vp, c_i64, c_vp]),
     "vit_copy2d": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp]),

@@ -100,6 +100,18 @@ def load_checkpoint(path):
     raise ValueError("checkpoint format {} not supported yet!".format(path.split(".")[-1]))
 
 
+EMA_KEY = "state_dict_ema"  # timm's key for the weight EMA inside a training checkpoint
+
+
+def load_checkpoint_ema(path):
+    """the EMA weights of a vitmi.train `.pth` written by an --ema-decay run; ValueError naming the file when it holds
+    none (a Flax `.npz` never does)"""
+    ckpt = torch.load(path, map_location="cpu", weights_only=True) if path.endswith("pth") else {}
+    if EMA_KEY not in ckpt:
+        raise ValueError(f"{path}: no '{EMA_KEY}' in this checkpoint (vitmi.train writes it with --ema-decay)")
+    return ckpt[EMA_KEY]
+
+
 def save_jax_to_pytorch(jax_path, save_path):
     """reference src/checkpoint.py:28-33 — write `<name>.pth` = {'state_dict': converted weights}."""
     model_name = os.path.basename(jax_path).split(".")[0]

@@ -22,6 +22,17 @@ src/config.py:57-104). Additions for the MI355X path, all optional:
   --mixup-alpha A, --cutmix-alpha A   (train) Mixup / CutMix per batch, lambda ~ Beta(A, A) (vitmi.augment.BatchMixer);
                          --mix-prob P (1.0) mixes a batch with probability P, --mix-switch-prob S (0.5) picks CutMix
                          with probability S when both alphas are set
+  --optimizer sgd|adamw  (train) sgd (default): momentum 0.9, the reference's fine-tune. adamw: vitmi.optim.EngineAdamW,
+                         one launch over the engine's flat buffer; --beta1 0.9 --beta2 0.999 --adam-eps 1e-8; --wd is
+                         its decoupled weight decay, applied to the weight matrices only (timm's rule: not to biases,
+                         LayerNorms, the position table, cls_token) unless --decay-all
+  --lr-schedule onecycle|cosine|auto   (train) cosine: linear warm-up over --warmup-steps, then cosine decay to 0 at
+                         --train-steps (vitmi.optim.get_cosine_schedule_with_warmup), stepped per optimizer step.
+                         auto (default): onecycle for sgd, cosine for adamw; onecycle with adamw is refused
+  --ema-decay D          (train) exponential moving average of the weights, ema = D ema + (1-D) w once per optimizer
+                         step (0: off); each epoch also validates the EMA weights (val_ema_*) and the checkpoint gains
+                         "state_dict_ema"
+  --use-ema              (eval) evaluate the checkpoint's "state_dict_ema"
 
 Without --synthetic, the reference's own commands run on CIFAR read from disk (vitmi.datasets, vitmi.data):
     python -m vitmi.train --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path w.pth ...
@@ -112,6 +123,8 @@ def get_eval_config(argv=None):
     parser.add_argument("--dataset", type=str, default="ImageNet", help="dataset for fine-tunning/evaluation")
     parser.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"],
                         help="bf16 MFMA forward or the reference's f32 arithmetic")
+    parser.add_argument("--use-ema", default=False, action="store_true",
+                        help="evaluate the checkpoint's EMA weights (state_dict_ema, saved by --ema-decay runs)")
     config = parser.parse_args(argv)
     _check_image_size(config)
     config = globals()["get_{}_config".format(config.model_arch)](config)
@@ -143,9 +156,21 @@ def get_train_config(argv=None):
     parser.add_argument("--clip-grad-norm", type=float, default=0.0,
                         help="clip the gradient to this global 2-norm before each update (0: off)")
     add_augment_args(parser, mixing=True)
+    parser.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adamw"],
+                        help="sgd: momentum 0.9 (the reference's fine-tune); adamw: vitmi.optim.EngineAdamW")
+    parser.add_argument("--beta1", type=float, default=0.9, help="adamw: beta1")
+    parser.add_argument("--beta2", type=float, default=0.999, help="adamw: beta2")
+    parser.add_argument("--adam-eps", type=float, default=1e-8, help="adamw: eps")
+    parser.add_argument("--decay-all", default=False, action="store_true",
+                        help="adamw: decay every parameter (default: not the biases, LayerNorms, position table, cls)")
+    parser.add_argument("--lr-schedule", type=str, default="auto", choices=["onecycle", "cosine", "auto"],
+                        help="auto: onecycle for sgd, cosine (linear warm-up, cosine decay to 0) for adamw")
+    parser.add_argument("--ema-decay", type=float, default=0.0,
+                        help="keep an exponential moving average of the weights with this decay (0: off)")
     config = parser.parse_args(argv)
     _check_image_size(config)
     check_augment_args(config)
+    check_optimizer_args(config)
     if config.accum_steps < 1 or config.batch_size % (config.accum_steps * max(1, config.n_gpu)):
         raise SystemExit(f"--batch-size {config.batch_size} is the batch of one optimizer step and must divide evenly "
                          f"into --accum-steps {config.accum_steps} micro-batches on each of {config.n_gpu} GPUs")
@@ -199,6 +224,21 @@ def check_augment_args(config):
     for flag, v in (("--mix-prob", config.mix_prob), ("--mix-switch-prob", config.mix_switch_prob)):
         if not 0.0 <= v <= 1.0:
             raise SystemExit(f"{flag} {v:g}: expected a value in [0, 1]")
+
+
+def check_optimizer_args(config):
+    """resolves --lr-schedule auto; a schedule that does not go with the optimizer and an out-of-range --ema-decay exit
+    with one line"""
+    if config.lr_schedule == "auto":
+        config.lr_schedule = "cosine" if config.optimizer == "adamw" else "onecycle"
+    if config.optimizer == "adamw" and config.lr_schedule == "onecycle":
+        raise SystemExit("--lr-schedule onecycle does not go with --optimizer adamw (OneCycleLR would cycle beta1); "
+                         "use cosine")
+    if not 0.0 <= config.ema_decay < 1.0:
+        raise SystemExit(f"--ema-decay {config.ema_decay:g}: expected a value in [0, 1) (0: off)")
+    for flag, v in (("--beta1", config.beta1), ("--beta2", config.beta2)):
+        if not 0.0 <= v < 1.0:
+            raise SystemExit(f"{flag} {v:g}: expected a value in [0, 1)")
 
 
 def _check_image_size(config):

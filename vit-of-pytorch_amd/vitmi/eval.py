@@ -8,7 +8,9 @@ under torch.no_grad() -> mean top-1 / top-5 over batches, printed in the referen
 Top-1 / top-5 come from the fused cross-entropy kernel's per-row hit counts (vit_cross_entropy,
 src/utils.py:28-41 semantics) instead of a topk pass. Sequences above 320 tokens (384 px: 577 for
 B/16 and L/16, 730 for H/14) run the K/V-tiled attention kernels. `--precision fp32` evaluates with
-the reference's own f32 arithmetic (vit_gemm_f32 projections, f32 attention).
+the reference's own f32 arithmetic (vit_gemm_f32 projections, f32 attention). `--use-ema` evaluates the weight EMA
+of a vitmi.train checkpoint written with --ema-decay (its "state_dict_ema"); a file without one stops the run with one
+line naming it.
 Data: `--dataset CIFAR10|CIFAR100 --data-dir D` evaluates the test split read from disk and kept in HBM
 (vitmi.datasets, vitmi.data.ResidentLoader), in file order; `--synthetic` a synthetic split, as in
 vitmi.train. `--dataset ImageNet` (the default) evaluates the image folder D/ImageNet/val/<class>/..., and
@@ -29,6 +31,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .checkpoint import load_checkpoint_ema
 from .config import get_eval_config
 from .train import SyntheticDataLoader, build_model, fit_pos_embedding, load_checkpoint, set_seed
 
@@ -52,6 +55,15 @@ def evaluate(model, data_loader, device):
 def main(argv=None):
     config = get_eval_config(argv)
     set_seed(config.seed)
+    ema_state = None
+    if config.use_ema:
+        # read first: a checkpoint without EMA weights stops the run with one line, before anything else is set up
+        if not config.checkpoint_path:
+            raise SystemExit("--use-ema needs --checkpoint-path")
+        try:
+            ema_state = load_checkpoint_ema(config.checkpoint_path)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
     if not torch.cuda.is_available():
         raise SystemExit("vitmi.eval needs a ROCm GPU (MI355X)")
     device = torch.device("cuda", 0)
@@ -63,9 +75,9 @@ def main(argv=None):
         data_loader, = loaders(config, config.batch_size, device, splits=("test",))
     model = build_model(config, device)
     if config.checkpoint_path:
-        state_dict = fit_pos_embedding(load_checkpoint(config.checkpoint_path), model, config)
-        model.load_state_dict(state_dict)
-        print("Load pretrained weights from {}".format(config.checkpoint_path))
+        state_dict = load_checkpoint(config.checkpoint_path) if ema_state is None else ema_state
+        model.load_state_dict(fit_pos_embedding(state_dict, model, config))
+        print("Load {} weights from {}".format("pretrained" if ema_state is None else "EMA", config.checkpoint_path))
     model = model.to(device)
     model.precision = config.precision
     if data_loader is None:

@@ -277,6 +277,32 @@ class VisionTransformer(nn.Module):
         finally:
             eng.grad_ready_hook, eng.grad_ready_finish = saved
 
+    @contextlib.contextmanager
+    def swapped_weights(self, flat):
+        """Run the model on another master buffer of the engine's flat layout (an optimizer's weight EMA): inside the
+        context the engine and every Parameter point at `flat` and the bf16 operands are rebuilt from it; on exit,
+        also after an exception, the trained weights are back and the operands rebuilt again. Same engine, same
+        activations. For evaluation: nothing inside may update the weights."""
+        eng = self.engine()
+        if flat.shape != eng.flat.shape or flat.dtype != eng.flat.dtype or flat.device != eng.flat.device or \
+                not flat.is_contiguous():
+            raise ValueError("swapped_weights: expected a contiguous buffer shaped like the engine's flat parameters")
+
+        def point_at(buf):
+            eng.flat = buf
+            with torch.no_grad():
+                for n, p in zip(self._flat_names, self._flat_params):
+                    p.data = eng.layout.view(buf, n)
+            eng.refresh_mirror(full=True)
+            eng.mark_mirror_fresh(self._version_sig())
+
+        trained = eng.flat
+        point_at(flat)
+        try:
+            yield self
+        finally:
+            point_at(trained)
+
     # ---- engine binding -----------------------------------------------------------------------
     def _bind_engine(self):
         """Move every parameter into the engine's flat buffer (Parameters become views of it)."""

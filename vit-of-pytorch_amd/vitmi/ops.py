@@ -680,6 +680,22 @@ def adamw_chunk_elems():
     return lib().vit_adamw_chunk_elems()
 
 
+def adamw_ema_update(p, g, m, v, p_bf16, ema, chunks, table, lr, beta1, beta2, eps, wd, ema_decay, write_grad):
+    """the ViT engine's AdamW step in one launch (vit_adamw_ema_update). chunks: int64 [nchunks, 3] = {flags, start,
+    length} in PINNED host memory (bit 0 of flags: decayed); table: vit_adamw_prep's float4 for nseg = 1. ema (and
+    ema_decay) or p_bf16 may be None."""
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema"), (table, "table")):
+        _chk(t, F32, name)
+    _chk(p_bf16, BF16, "p_bf16")
+    if chunks.is_cuda or chunks.dtype != torch.int64 or not chunks.is_contiguous() or not chunks.is_pinned():
+        raise ValueError("adamw_ema_update: chunks must be a contiguous int64 tensor in pinned host memory")
+    # (1 - lr*wd), (1 - beta) and (1 - ema_decay) in double, then rounded: torch's Python-scalar arithmetic
+    check(lib().vit_adamw_ema_update(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(ema), _p(chunks), chunks.numel() // 3,
+                                     _p(table), 1.0 - lr * wd, beta1, beta2, 1.0 - beta1, 1.0 - beta2, eps,
+                                     0.0 if ema is None else 1.0 - ema_decay, int(write_grad), _stream()),
+          "vit_adamw_ema_update")
+
+
 def scale_by_coef(g, n, coef):
     check(lib().vit_scale_by_coef(_p(g), n, _p(coef), _stream()), "vit_scale_by_coef")
 

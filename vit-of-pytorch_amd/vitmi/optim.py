@@ -14,10 +14,15 @@ updated by the same kernel individually.
 gradient's 2-norm reduced on the device, coef = min(1, max_norm / (norm + 1e-6)), the flat gradient scaled by it in
 place (so .grad is left clipped), then the step. Under data parallelism step() runs after the reduced gradients are
 complete, so every rank clips by the same norm.
+
+`ema_decay` (fast path only) keeps a weight EMA, ema = d ema + (1 - d) p, with one vit_axpby launch after the update;
+without it the step issues exactly the launches it always did. EngineAdamW (below) is the from-scratch optimizer:
+torch.optim.AdamW over the same flat buffer, with the EMA inside its one update launch.
 """
 from __future__ import annotations
 
 import math
+from collections import OrderedDict
 
 import torch
 from torch.autograd.graph import increment_version
@@ -27,7 +32,7 @@ from . import ops
 
 class SGD(torch.optim.SGD):
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, model=None,
-                 max_grad_norm=None):
+                 max_grad_norm=None, ema_decay=None):
         if dampening != 0.0 or nesterov:
             raise NotImplementedError("vitmi.optim.SGD implements dampening=0, nesterov=False (the reference config)")
         super().__init__(params, lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
@@ -38,6 +43,14 @@ class SGD(torch.optim.SGD):
         self.max_grad_norm = max_grad_norm
         self._parts = None
         self.last_norm = None  # device {total grad norm, clip coefficient} of the last clipped step
+        # weight EMA (fast path only): a copy of the engine's flat buffer taken here, so construct the optimizer after
+        # the checkpoint load and the rank-0 broadcast; ema = d * ema + (1 - d) * p after every step (one vit_axpby)
+        self.ema_decay = _check_ema_decay(ema_decay)
+        self.ema = _engine_of(model, "SGD(ema_decay=...)").flat.clone() if self.ema_decay is not None else None
+
+    def ema_state_dict(self):
+        """the model's state_dict() layout over the EMA weights (copies)"""
+        return _ema_state_dict(self._model, self.ema)
 
     def _flat_engine(self):
         m = self._model
@@ -79,14 +92,16 @@ class SGD(torch.optim.SGD):
             ops.sgd_step(eng.flat, eng.grad, self._flat_buf, eng.mirror, eng.layout.numel, g["lr"], g["momentum"],
                          g["weight_decay"], self._flat_first)
             self._flat_first = False
+            if self.ema is not None:
+                ops.axpby(eng.flat, self.ema, eng.layout.numel, 1.0 - self.ema_decay, self.ema_decay)
             eng.refresh_mirror(full=False)           # repack q/k/v (+ padded conv) from updated masters
             eng.mark_mirror_fresh(self._model._version_sig())
             return loss
-        if self.max_grad_norm is not None:
+        if self.max_grad_norm is not None or self.ema is not None:
             raise NotImplementedError(
-                "vitmi.optim.SGD(max_grad_norm=...) clips on the flat fast path only: the optimizer must hold exactly "
-                "the parameters of its `model` (one bound vitmi VisionTransformer) in one param group, and every "
-                ".grad must be the engine's flat gradient buffer")
+                "vitmi.optim.SGD(max_grad_norm=... / ema_decay=...) runs on the flat fast path only: the optimizer "
+                "must hold exactly the parameters of its `model` (one bound vitmi VisionTransformer) in one param "
+                "group, and every .grad must be the engine's flat gradient buffer")
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
@@ -101,6 +116,190 @@ class SGD(torch.optim.SGD):
                 ops.sgd_step(p, p.grad, buf, None, p.numel(), group["lr"], group["momentum"], group["weight_decay"],
                              first)
                 increment_version(p)  # raw-pointer update: let version-keyed bf16 mirrors see it
+        return loss
+
+
+# ---- from-scratch training: AdamW over the engine's flat buffer, decay groups, weight EMA ----------------------------
+def _check_ema_decay(d):
+    if d is None:
+        return None
+    d = float(d)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay {d:g}: expected a value in [0, 1)")
+    return d
+
+
+def _engine_of(model, what):
+    """the engine of a VisionTransformer on the GPU (bound if it was not), or NotImplementedError"""
+    if model is None or not hasattr(model, "_bind_engine"):
+        raise NotImplementedError(f"vitmi.optim.{what} needs model= (one vitmi VisionTransformer on the GPU)")
+    return model.engine()
+
+
+def _ema_state_dict(model, ema):
+    if ema is None:
+        raise RuntimeError("ema_state_dict(): the optimizer was built without ema_decay")
+    lay = model.engine().layout
+    return OrderedDict((k, lay.view(ema, k).clone()) for k in model.state_dict().keys())
+
+
+ADAMW_CHUNK = 8192  # vit_adamw_chunk_elems()
+
+
+def no_decay_names(layout):
+    """timm's rule over a FlatLayout: parameters of at most one dimension (LayerNorm weights and biases, the Linear and
+    conv biases), every `.bias` (the LinearGeneral biases are 2-D), the position table and cls_token"""
+    return [n for n, shape in layout.shapes.items()
+            if len(shape) <= 1 or n.endswith(".bias") or n in ("transformer.pos_embedding.pos_embedding", "cls_token")]
+
+
+def adamw_chunk_table(layout, decay_all=False, chunk=ADAMW_CHUNK):
+    """int64 [nchunks, 3] = {flags, start, length <= chunk} of vit_adamw_ema_update over a FlatLayout (bit 0 of flags:
+    decayed). Neighbouring parameters of one kind form a run, the alignment padding behind a parameter rides with it
+    (it is zero in every buffer and the update keeps it zero), and every run is cut into chunks: all starts and
+    lengths are multiples of the 64-element alignment. Host arithmetic only."""
+    skip = set() if decay_all else set(no_decay_names(layout))
+    names = list(layout.offsets)
+    ends = [layout.offsets[n] for n in names[1:]] + [layout.numel]
+    runs = []  # [flag, start, end)
+    for n, end in zip(names, ends):
+        flag = int(n not in skip)
+        if runs and runs[-1][0] == flag:
+            runs[-1][2] = end
+        else:
+            runs.append([flag, layout.offsets[n], end])
+    rows = [[flag, at, min(chunk, end - at)] for flag, start, end in runs for at in range(start, end, chunk)]
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 3)
+
+
+class EngineAdamW(torch.optim.AdamW):
+    """torch.optim.AdamW (decoupled decay, bias correction; no amsgrad / maximize) for one vitmi VisionTransformer,
+    stepping the engine's whole flat buffer in ONE launch (vit_adamw_ema_update): the clip scale, the decay (timm's
+    groups: no_decay_names() are not decayed; decay_all=True is torch's plain single group), both moments, the update,
+    the weight EMA and the bf16 GEMM mirror. Like SGD's fast path it needs exactly the parameters of `model` in one
+    group, with every .grad the engine's flat gradient; there is no per-tensor path.
+
+    max_grad_norm clips as torch.nn.utils.clip_grad_norm_(params, max_norm, 2) would (the clipped gradient is written
+    back to .grad); last_norm keeps the device {norm, coefficient}. ema_decay keeps ema = d ema + (1 - d) p after every
+    step, in a copy of the flat buffer taken at construction: build the optimizer after the checkpoint load and the
+    rank-0 broadcast. Every parameter gets a gradient every step, so `step` is one device scalar shared by all."""
+
+    _flat_engine = SGD._flat_engine
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, model=None,
+                 max_grad_norm=None, ema_decay=None, decay_all=False):
+        eng = _engine_of(model, "EngineAdamW")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._model = model
+        ps = self.param_groups[0]["params"]
+        if len(self.param_groups) != 1 or len(ps) != len(model._flat_params) or \
+                set(map(id, ps)) != set(map(id, model._flat_params)):
+            raise NotImplementedError(self._NEEDS)
+        self.max_grad_norm = max_grad_norm
+        self.decay_all = bool(decay_all)
+        self.ema_decay = _check_ema_decay(ema_decay)
+        assert ops.adamw_chunk_elems() == ADAMW_CHUNK
+        self._chunks = adamw_chunk_table(eng.layout, self.decay_all).pin_memory()
+        self.exp_avg = torch.zeros_like(eng.flat)
+        self.exp_avg_sq = torch.zeros_like(eng.flat)
+        self.ema = eng.flat.clone() if self.ema_decay is not None else None
+        self.steps = torch.zeros(1, device=eng.dev)
+        self._used = torch.ones(1, device=eng.dev)
+        self._table = torch.zeros(4, device=eng.dev)
+        n = eng.layout.numel
+        self._parts = torch.zeros(max(1, min(1024, math.ceil(n / (256 * 4 * 16)))), device=eng.dev, dtype=torch.float64)
+        self.last_norm = torch.zeros(2, device=eng.dev) if max_grad_norm is not None else None
+        self._stepped = False
+        for name, p in zip(model._flat_names, model._flat_params):
+            self.state[p] = {"step": self.steps[0], "exp_avg": eng.layout.view(self.exp_avg, name),
+                             "exp_avg_sq": eng.layout.view(self.exp_avg_sq, name)}
+
+    _NEEDS = ("vitmi.optim.EngineAdamW steps the engine's flat buffer only: it must hold exactly the parameters of its "
+              "`model` (one bound vitmi VisionTransformer) in one param group, and every .grad must be the engine's "
+              "flat gradient buffer")
+
+    def ema_state_dict(self):
+        """the model's state_dict() layout over the EMA weights (copies)"""
+        return _ema_state_dict(self._model, self.ema)
+
+    def _groups(self):
+        """the parameters as torch.optim.AdamW would group them: [all], or [decayed, not decayed], in group order"""
+        ps = self.param_groups[0]["params"]
+        if self.decay_all:
+            return [ps]
+        skip = set(no_decay_names(self._model._engine.layout))
+        name = {id(p): n for n, p in zip(self._model._flat_names, self._model._flat_params)}
+        return [[p for p in ps if name[id(p)] not in skip], [p for p in ps if name[id(p)] in skip]]
+
+    def state_dict(self):
+        """torch.optim.AdamW's format: one group under decay_all, otherwise the decayed parameters' group and the
+        others' with weight_decay 0 (both in this optimizer's parameter order); state[i] = {step, exp_avg,
+        exp_avg_sq} (copies) once a step has run. It loads into a torch.optim.AdamW built over the same groups."""
+        base = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        lay = self._model._engine.layout
+        name = {id(p): n for n, p in zip(self._model._flat_names, self._model._flat_params)}
+        groups, state, k = [], {}, 0
+        step = self.steps[0].detach().cpu() if self._stepped else None  # (torch keeps `step` on the host)
+        for gi, plist in enumerate(self._groups()):
+            groups.append(dict(base, weight_decay=base["weight_decay"] if gi == 0 else 0.0,
+                               params=list(range(k, k + len(plist)))))
+            for p in plist:
+                if self._stepped:
+                    state[k] = {"step": step.clone(),
+                                "exp_avg": lay.view(self.exp_avg, name[id(p)]).clone(),
+                                "exp_avg_sq": lay.view(self.exp_avg_sq, name[id(p)]).clone()}
+                k += 1
+        return {"state": state, "param_groups": groups}
+
+    def load_state_dict(self, state_dict):
+        """copy a state of state_dict()'s form (this class's or torch.optim.AdamW's over the same groups) into the
+        flat moment buffers and the step; the hyper-parameters come from its first group"""
+        lists = self._groups()
+        groups = state_dict["param_groups"]
+        if [len(g["params"]) for g in groups] != [len(pl) for pl in lists]:
+            raise ValueError("vitmi.optim.EngineAdamW.load_state_dict: expected groups of %s parameters"
+                             % [len(pl) for pl in lists])
+        for k, v in groups[0].items():
+            if k != "params":
+                self.param_groups[0][k] = v
+        lay = self._model._engine.layout
+        name = {id(p): n for n, p in zip(self._model._flat_names, self._model._flat_params)}
+        steps = set()
+        for g, plist in zip(groups, lists):
+            for k, p in zip(g["params"], plist):
+                st = state_dict["state"].get(k, state_dict["state"].get(str(k)))
+                for buf, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
+                    v = lay.view(buf, name[id(p)])
+                    v.zero_() if st is None else v.copy_(st[key].reshape(v.shape))
+                steps.add(0.0 if st is None else float(st["step"]))
+        if len(steps) != 1:
+            raise ValueError("vitmi.optim.EngineAdamW.load_state_dict: the parameters' step counts differ "
+                             f"({sorted(steps)}); this optimizer keeps one")
+        self.steps.fill_(steps.pop())
+        self._stepped = float(self.steps[0]) > 0
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        eng = self._flat_engine()
+        if eng is None:
+            raise NotImplementedError(self._NEEDS)
+        g = self.param_groups[0]
+        beta1, beta2 = g["betas"]
+        clip = self.max_grad_norm is not None
+        if clip:  # (the alignment padding of the flat gradient is zero: it adds nothing to the norm)
+            ops.sqnorm_partial(eng.grad, eng.layout.numel, self._parts)
+        ops.adamw_prep(self._parts if clip else None, self._used, self.steps, float(g["lr"]), float(beta1),
+                       float(beta2), float(self.max_grad_norm or 0.0), self._table, self.last_norm)
+        ops.adamw_ema_update(eng.flat, eng.grad, self.exp_avg, self.exp_avg_sq, eng.mirror, self.ema, self._chunks,
+                             self._table, float(g["lr"]), float(beta1), float(beta2), float(g["eps"]),
+                             float(g["weight_decay"]), self.ema_decay, clip)
+        self._stepped = True
+        eng.refresh_mirror(full=False)           # repack q/k/v (+ padded conv) from updated masters
+        eng.mark_mirror_fresh(self._model._version_sig())
         return loss
 
 

@@ -43,6 +43,15 @@ save_model (:69-81), main (:84-194); MetricTracker / the step writer follow src/
     uses plain cross entropy.
   * `--clip-grad-norm X` clips the accumulated (and, data parallel, reduced) gradient to global 2-norm X before the
     update (vitmi.optim.SGD(max_grad_norm=X)).
+  * `--optimizer adamw` (default sgd, the step as it was) steps with vitmi.optim.EngineAdamW: clip scale, decoupled
+    decay on the weight matrices only (timm's rule; `--decay-all` for torch's single group), moments, update, weight EMA
+    and bf16 mirror in one launch over the flat buffer. Its schedule is `--lr-schedule cosine` (linear warm-up over
+    --warmup-steps, cosine decay to 0 at --train-steps; `auto` picks it for adamw and onecycle for sgd).
+  * `--ema-decay D` keeps ema = D ema + (1 - D) w, updated once per optimizer step (inside the AdamW launch; one
+    vit_axpby under sgd). Each epoch validates the EMA weights too, through VisionTransformer.swapped_weights (same
+    engine, same activations), logged as val_ema_loss / val_ema_acc1 / val_ema_acc5; the checkpoint gains
+    "state_dict_ema" (timm's key; vitmi.eval --use-ema reads it). best.pth keeps following val_acc1. Optimizer, EMA
+    and scheduler states are saved in loadable form; resuming a run is not implemented.
 """
 from __future__ import annotations
 
@@ -61,7 +70,7 @@ from . import checkpoint as _ckpt
 from .config import get_train_config, image_hw
 from .dist import GradAllReducer
 from .model import CrossEntropyLoss, VisionTransformer
-from .optim import SGD
+from .optim import SGD, EngineAdamW, get_cosine_schedule_with_warmup
 
 
 def set_seed(seed=42):
@@ -359,6 +368,8 @@ def save_model(save_dir, epoch, model, optimizer, lr_scheduler, device_ids=(), b
         "optimizer": optimizer.state_dict(),
         "lr_scheduler": lr_scheduler.state_dict(),
     }
+    if getattr(optimizer, "ema", None) is not None:  # timm's key; absent without --ema-decay
+        state[_ckpt.EMA_KEY] = optimizer.ema_state_dict()
     torch.save(state, str(save_dir + "current.pth"))
     if best:
         torch.save(state, str(save_dir + "best.pth"))
@@ -507,11 +518,22 @@ def main(argv=None):
         from .augment import BatchMixer
         mixer = BatchMixer(config.mixup_alpha, config.cutmix_alpha, config.mix_prob, config.mix_switch_prob,
                            seed=config.seed + rank)
-    optimizer = SGD(params=model.parameters(), lr=config.lr, weight_decay=config.wd, momentum=0.9, model=model,
-                    max_grad_norm=config.clip_grad_norm if config.clip_grad_norm > 0 else None)
-    lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer=optimizer, max_lr=config.lr,
-                                                       pct_start=config.warmup_steps / config.train_steps,
-                                                       total_steps=config.train_steps)
+    # (after the checkpoint load and the broadcast: an EMA starts as a copy of the weights as they are now; every rank
+    #  then computes the same EMA from the same reduced gradients)
+    shared = dict(params=model.parameters(), lr=config.lr, weight_decay=config.wd, model=model,
+                  max_grad_norm=config.clip_grad_norm if config.clip_grad_norm > 0 else None,
+                  ema_decay=config.ema_decay if config.ema_decay > 0 else None)
+    if config.optimizer == "adamw":
+        optimizer = EngineAdamW(betas=(config.beta1, config.beta2), eps=config.adam_eps, decay_all=config.decay_all,
+                                **shared)
+    else:
+        optimizer = SGD(momentum=0.9, **shared)
+    if config.lr_schedule == "cosine":
+        lr_scheduler = get_cosine_schedule_with_warmup(optimizer, config.warmup_steps, config.train_steps)
+    else:
+        lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer=optimizer, max_lr=config.lr,
+                                                           pct_start=config.warmup_steps / config.train_steps,
+                                                           total_steps=config.train_steps)
     writer = StepWriter(config.summary_dir, config.swanlab)
     metric_names = ["loss", "acc1", "acc5"]
     train_metrics = MetricTracker(*metric_names, writer=writer)
@@ -529,6 +551,10 @@ def main(argv=None):
         model.eval()
         result = valid_epoch(epoch, model, valid_loader, valid_criterion, valid_metrics, device)
         log.update(**{"val_" + k: v for k, v in result.items()})
+        if optimizer.ema is not None:  # the same split through the EMA weights; best.pth keeps following val_acc1
+            with model.swapped_weights(optimizer.ema):
+                result = valid_epoch(epoch, model, valid_loader, valid_criterion, valid_metrics, device)
+            log.update(**{"val_ema_" + k: v for k, v in result.items()})
         best = log["val_acc1"] > best_acc
         if best:
             best_acc = log["val_acc1"]
