@@ -213,6 +213,46 @@ int vit_layernorm_bwd(const void* dy, int64_t lddy, int32_t dy_f32, const float*
                       const vit_dropout* dx_dropout, vit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Stochastic depth (DropPath), timm.layers.drop_path with scale_by_keep: a residual branch's output is multiplied,
+ * per sample, by 0 with probability p and by 1 / (1 - p) otherwise, before it joins the residual stream.
+ * (ABI 24, additions only: vit_dropout, vit_gemm_args, vit_gemm_bf16 and vit_layernorm_bwd are unchanged.)
+ *
+ * The draw stays inside the dropout scheme above: the multiplier of sample b at branch site s (the engine numbers
+ * them 2i = attention branch, 2i + 1 = MLP branch of encoder layer i) is the dropout multiplier of element
+ * (row b, col 0) of dropout site 0x80000000 | s under the same (seed, offset). Dropout's own sites never set the
+ * top bit, so the streams do not collide, and vit_dropout_mask on that site restates the table.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct vit_drop_path {
+  const float* scale;       /* device, one f32 per sample: 0 or 1/(1-p) */
+  int64_t rows_per_sample;  /* sample of the call's row r = r / rows_per_sample (>= 1) */
+} vit_drop_path;
+/* scale[s*B + b] = multiplier of sample b at site s with rate p_site[s] (host array; every rate in [0, 1)); all ones
+ * where p_site[s] == 0. One launch, no host synchronisation. nsites <= VIT_DROP_PATH_MAX_SITES. */
+#define VIT_DROP_PATH_MAX_SITES 128
+int vit_drop_path_scales(const float* p_site, int32_t nsites, int64_t B, uint64_t seed, uint64_t offset, float* scale,
+                         vit_stream_t stream);
+/* vit_gemm_bf16 with the per-sample multiplier on the branch: VIT_EPI_BIAS_RESID_F32 only,
+ *   C = drop(acc + bias) * path->scale[m / rows_per_sample] + aux      (drop = args->dropout, or the identity)
+ * with m the call's row (a wave-split remainder launch indexes by the absolute row). A K-contiguous; B in either
+ * layout; C == aux allowed; the same tile selection and wave split as vit_gemm_bf16. path == NULL is exactly
+ * vit_gemm_bf16(args). */
+int vit_gemm_bf16_drop_path(const vit_gemm_args* args, const vit_drop_path* path, vit_stream_t stream);
+/* vit_layernorm_bwd whose bf16 copy, dx_colsum and block partials of dx carry
+ *   dx_out * dropout_mult * dx_path->scale[mask_row / rows_per_sample],
+ * mask_row = the dropout descriptor's mask row of the call's row r (r * row_stride; r itself without dx_dropout).
+ * dx itself is unchanged. dx_path == NULL is exactly vit_layernorm_bwd. */
+int vit_layernorm_bwd_drop_path(const void* dy, int64_t lddy, int32_t dy_f32, const float* x, int64_t ldx,
+                                const float* mean, const float* rstd, const float* gamma,
+                                const float* dres, int64_t lddres, float* dx, int64_t lddx,
+                                void* dx_bf16, int64_t lddxb, float* partial, float* dgamma_dbeta,
+                                float* dx_colsum, int32_t accumulate_params, int64_t rows, int64_t D,
+                                const vit_dropout* dx_dropout, const vit_drop_path* dx_path, vit_stream_t stream);
+/* out[r*cols + c] = in[r*cols + c] * scale[r / rows_per_sample] (in == out allowed): forward and backward of a
+ * standalone DropPath module */
+int vit_row_scale_f32(const float* in, float* out, int64_t rows, int64_t cols, const float* scale,
+                      int64_t rows_per_sample, vit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused multi-head self-attention, one (image, head) per workgroup, all keys in LDS.
  * qkv: bf16 [B*N, 3, H, hd] (q | k | v);  o: bf16 [B*N, H, hd];  lse: f32 [B, H, N]
  * S = (q k^T) * scale (scale = 1/sqrt(hd)), P = softmax(S), O = P v.

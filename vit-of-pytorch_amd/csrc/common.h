@@ -120,6 +120,33 @@ __device__ __forceinline__ float drop_mult1(const DropDev& d, long row, int col)
   return ((r[k >> 1] >> (16 * (k & 1))) & 0xffffu) >= d.thr ? d.scale : 0.0f;
 }
 
+// ---- stochastic depth: one multiplier per sample on a residual branch (see vit_drop_path in vit_hip.h) ----
+// sample of row r = r / rps as a multiply-high and a shift (exact for r < 2^31): two instructions per row where
+// the hardware has no integer divide. mul = ceil(2^(31 + l) / rps), shr = l - 1, l = ceil(log2 rps); rps == 1
+// (whose multiplier would need 33 bits) is the identity.
+struct PathDev {
+  const float* scale;  // null: no drop-path
+  uint32_t mul, shr;
+  int rps;
+};
+static inline PathDev make_path(const vit_drop_path* d) {
+  PathDev r = {nullptr, 0u, 0u, 1};
+  if (!d) return r;
+  r.scale = d->scale;
+  r.rps = (int)d->rows_per_sample;
+  if (r.rps > 1) {
+    uint32_t l = 0;
+    while ((1ull << l) < (uint64_t)r.rps) ++l;
+    const uint64_t two_p = 1ull << (31 + l);
+    r.mul = (uint32_t)((two_p + (uint64_t)r.rps - 1) / (uint64_t)r.rps);
+    r.shr = l - 1;
+  }
+  return r;
+}
+__device__ __forceinline__ uint32_t path_sample(const PathDev& d, uint32_t row) {
+  return d.rps == 1 ? row : __umulhi(row, d.mul) >> d.shr;
+}
+
 // ---- host-side error plumbing (thread-local last error, int status returns) ----
 namespace vit {
 void set_error(const char* fmt, ...);

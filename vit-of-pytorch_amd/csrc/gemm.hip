@@ -24,6 +24,7 @@
 namespace {
 using vitg::GemmDev;
 using vitg::EPI_DROP;
+using vitg::EPI_PATH;
 
 int pick_tile(const vit_gemm_args* a) {
   if (a->tile > 0) return (int)a->tile;
@@ -231,10 +232,21 @@ int make_dev(const vit_gemm_args* a, GemmDev& d, bool& empty) {
 
 // part 0: the whole GEMM; 1: its whole-wave rows (all of it when it does not split); 2: the wave-split remainder
 // rows (nothing when it does not split)
-int gemm_bf16_impl(const vit_gemm_args* a, int part, vit_stream_t stream) {
+// path: the stochastic-depth descriptor of vit_gemm_bf16_drop_path (null: the plain kernels)
+int gemm_bf16_impl(const vit_gemm_args* a, int part, vit_stream_t stream, const vit_drop_path* path = nullptr) {
   GemmDev d;
   bool empty = false;
   if (const int rc = make_dev(a, d, empty)) return rc;
+  if (path) {
+    VIT_CHECK_ARG(a->epilogue == VIT_EPI_BIAS_RESID_F32, "vit_gemm_bf16_drop_path: VIT_EPI_BIAS_RESID_F32 only");
+    VIT_CHECK_ARG(a->a_layout == VIT_K_CONTIG && a->batch == 1, "vit_gemm_bf16_drop_path: needs a K-contiguous A, batch 1");
+    VIT_CHECK_ARG(path->scale && path->rows_per_sample >= 1 && path->rows_per_sample < (1L << 31),
+                  "vit_gemm_bf16_drop_path: needs a scale table and rows_per_sample >= 1");
+    const PathDev pd = make_path(path);  // carried in fields this epilogue does not read (EPI_PATH, gemm_decl.h)
+    d.aux2 = pd.scale;
+    d.tokens = pd.rps;
+    d.ldc2 = (long)pd.mul | ((long)pd.shr << 32);
+  }
   if (empty) return VIT_OK;
   const bool ak = a->a_layout == VIT_K_CONTIG, bk = a->b_layout == VIT_K_CONTIG;
   if (a->col_partial) {
@@ -260,6 +272,10 @@ int gemm_bf16_impl(const vit_gemm_args* a, int part, vit_stream_t stream) {
       case VIT_EPI_BIAS_BF16: return vitg::launch_layout_x<VIT_EPI_BIAS_BF16>(c, g, ak, bk, batch, split, s);
       case VIT_EPI_BIAS_GELU: return vitg::launch_layout_x<VIT_EPI_BIAS_GELU>(c, g, ak, bk, batch, split, s);
       case VIT_EPI_BIAS_RESID_F32:
+        if (path)
+          return g.drop.thr
+                     ? vitg::launch_kk_x<VIT_EPI_BIAS_RESID_F32 | EPI_DROP | EPI_PATH>(c, g, bk, batch, split, s)
+                     : vitg::launch_kk_x<VIT_EPI_BIAS_RESID_F32 | EPI_PATH>(c, g, bk, batch, split, s);
         if (g.drop.thr) return vitg::launch_kk_x<VIT_EPI_BIAS_RESID_F32 | EPI_DROP>(c, g, bk, batch, split, s);
         return vitg::launch_layout_x<VIT_EPI_BIAS_RESID_F32>(c, g, ak, bk, batch, split, s);
       case VIT_EPI_GELU_BWD: return vitg::launch_layout_x<VIT_EPI_GELU_BWD>(c, g, ak, bk, batch, split, s);
@@ -292,7 +308,7 @@ int gemm_bf16_impl(const vit_gemm_args* a, int part, vit_stream_t stream) {
     if (d.C2) g2.C2 = (char*)d.C2 + r0 * a->ldc2 * 2;
     if (d.aux) g2.aux = (const char*)d.aux + r0 * a->ldaux * (a->epilogue == VIT_EPI_BIAS_RESID_F32 ? 4 : 2);
     if (d.col_partial) g2.col_partial = d.col_partial + (main_rows / 256) * a->N;
-    g2.drop.row0 = (int)r0;  // dropout masks are indexed by the absolute row
+    g2.drop.row0 = (int)r0;  // dropout masks (and drop-path samples) are indexed by the absolute row
     hipError_t e = hipSuccess;
     if (part != 2) e = run(cfg, g1);
     if (e == hipSuccess && part != 1) e = run(rem_config(), g2);
@@ -304,6 +320,10 @@ int gemm_bf16_impl(const vit_gemm_args* a, int part, vit_stream_t stream) {
 }  // namespace
 
 extern "C" int vit_gemm_bf16(const vit_gemm_args* a, vit_stream_t stream) { return gemm_bf16_impl(a, 0, stream); }
+
+extern "C" int vit_gemm_bf16_drop_path(const vit_gemm_args* a, const vit_drop_path* path, vit_stream_t stream) {
+  return gemm_bf16_impl(a, 0, stream, path);
+}
 
 extern "C" int vit_gemm_bf16_part(const vit_gemm_args* a, int32_t part, vit_stream_t stream) {
   VIT_CHECK_ARG(part == 1 || part == 2, "vit_gemm_bf16_part: part %d (1 = whole-wave rows, 2 = remainder)", part);

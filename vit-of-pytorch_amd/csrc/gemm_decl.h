@@ -35,14 +35,15 @@ struct GemmDev {
   long ldc;   // (VIT_EPI_SPLITK: the row stride of a slab, N; a direct group member's own output row stride)
   long c_bs;  // (VIT_EPI_SPLITK: the stride between (batch, split) slabs, M N; a direct member's batch stride)
   void* C2;
-  long ldc2;
+  long ldc2;   // (EPI_PATH launches, BIAS_RESID_F32 only: the PathDev's mul | shr << 32, see EPI_PATH below. An epilogue
+               //  that starts to read C2 / ldc2, aux2 or tokens under BIAS_RESID_F32 must move the PathDev first)
   const float* bias;
   long bias_bs;
   const void* aux;
   long ldaux;
-  const float* aux2;
+  const float* aux2;  // (EPI_PATH launches: the PathDev's scale table)
   int split_k;
-  int tokens;
+  int tokens;  // (EPI_PATH launches: the PathDev's rows per sample)
   int vec;  // every pointer / leading dim allows 8-column (16/32-B) vector access
   float* col_partial;  // optional per-M-tile column sums of the output
   int group_m;         // tile order: groups of group_m tile rows, column-major inside (0: row-major)
@@ -83,6 +84,13 @@ constexpr int EPI_DROP = 16;
 // destination (GemmDev::acc, wave-uniform per member); again its own instantiation, so the overwriting launch
 // carries neither the destination reads nor the branch
 constexpr int EPI_ACC = 32;
+// Internal epilogue flag, VIT_EPI_BIAS_RESID_F32 only (alone or with EPI_DROP): stochastic depth, the branch times
+// the per-sample multiplier before the residual add (vit_gemm_bf16_drop_path). Its own instantiations in their own
+// units (gemm_e10 / gemm_e11), so no other kernel carries the multiplier's load or a branch on it. GemmDev keeps its
+// size and layout (a larger kernel argument changed the register allocation of the kernels that run today): an
+// EPI_PATH launch carries its PathDev in three fields BIAS_RESID_F32 does not read, aux2 = scale, tokens = rows per
+// sample, ldc2 = mul | shr << 32 (set_path / path_mult), and drop.row0 makes a remainder launch's row absolute
+constexpr int EPI_PATH = 64;
 
 // launchers, one translation unit per epilogue (gemm_e<EPI>.hip) so the build parallelises
 template <int EPI>
@@ -102,5 +110,7 @@ template <> hipError_t launch_layout_x<9>(int, const GemmDev&, bool, bool, int, 
 template <> hipError_t launch_kk_x<20>(int, const GemmDev&, bool, int, int, hipStream_t);
 template <> hipError_t launch_kk_x<22>(int, const GemmDev&, bool, int, int, hipStream_t);
 template <> hipError_t launch_kk_x<24>(int, const GemmDev&, bool, int, int, hipStream_t);
+template <> hipError_t launch_kk_x<68>(int, const GemmDev&, bool, int, int, hipStream_t);
+template <> hipError_t launch_kk_x<84>(int, const GemmDev&, bool, int, int, hipStream_t);
 }  // namespace vitg
 

@@ -152,11 +152,22 @@ __device__ __forceinline__ void wait_vm() {
 
 using vitg::EPI_DROP;
 using vitg::EPI_ACC;
+using vitg::EPI_PATH;
 
+// stochastic depth (EPI_PATH): the multiplier of row m's sample, one load per row (chunk), never per element
+// (the PathDev rides in aux2 / tokens / ldc2, see EPI_PATH in gemm_decl.h)
+__device__ __forceinline__ float path_mult(const GemmDev& p, int m) {
+  const PathDev d = {p.aux2, (uint32_t)p.ldc2, (uint32_t)(p.ldc2 >> 32), p.tokens};
+  return d.scale[path_sample(d, (uint32_t)(m + p.drop.row0))];
+}
+
+// ps: the row's stochastic-depth multiplier (EPI_PATH instantiations; the caller loads it once per row chunk)
 template <int EPI>
-__device__ __forceinline__ void epi_store(const GemmDev& p, int z, int split_idx, int m, int n, float v) {
+__device__ __forceinline__ void epi_store(const GemmDev& p, int z, int split_idx, int m, int n, float v,
+                                          float ps = 1.0f) {
   constexpr int E = EPI & 15;                  // base epilogue
   constexpr bool DROP = (EPI & EPI_DROP) != 0;  // dropout variant
+  constexpr bool PATH = (EPI & EPI_PATH) != 0;  // stochastic-depth variant (BIAS_RESID_F32)
   if (m >= p.M || n >= p.N) return;
   if constexpr (E == VIT_EPI_F32) {
     float* C = (float*)p.C + z * p.c_bs;
@@ -179,7 +190,10 @@ __device__ __forceinline__ void epi_store(const GemmDev& p, int z, int split_idx
     const float* R = (const float*)p.aux;
     const float b = p.bias ? p.bias[z * p.bias_bs + n] : 0.f;
     const float dm = DROP ? drop_mult1(p.drop, m, n) : 1.0f;
-    C[(long)m * p.ldc + n] = (v + b) * dm + R[(long)m * p.ldaux + n];
+    if constexpr (PATH)
+      C[(long)m * p.ldc + n] = (v + b) * dm * ps + R[(long)m * p.ldaux + n];
+    else
+      C[(long)m * p.ldc + n] = (v + b) * dm + R[(long)m * p.ldaux + n];
   } else if constexpr (E == VIT_EPI_GELU_BWD) {
     bf16_t* C = (bf16_t*)p.C + z * p.c_bs;
     const bf16_t* U = (const bf16_t*)p.aux;
@@ -277,9 +291,10 @@ __device__ __forceinline__ void gelu_dgelu2(f2v u, f2v& gelu, f2v& dgelu) {
 // pre: the 8 aux values of (m, n..n+7) already loaded by the caller (GELU_BWD / MUL / RESID), or null.
 template <int EPI>
 __device__ __forceinline__ void epi_store8(const GemmDev& p, int z, int split_idx, int m, int n, float* v,
-                                           const float* pre = nullptr) {
+                                           const float* pre = nullptr, float ps = 1.0f) {
   constexpr int E = EPI & 15;
   constexpr bool DROP = (EPI & EPI_DROP) != 0;
+  constexpr bool PATH = (EPI & EPI_PATH) != 0;
   float b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if constexpr (E == VIT_EPI_BIAS_BF16 || E == VIT_EPI_BIAS_GELU || E == VIT_EPI_BIAS_RESID_F32 ||
                 E == VIT_EPI_BIAS_GELU_DGELU) {
@@ -310,7 +325,15 @@ __device__ __forceinline__ void epi_store8(const GemmDev& p, int z, int split_id
     } else {
       ld8f((const float*)p.aux + (long)m * p.ldaux + n, r);
     }
-    if constexpr (DROP) {
+    if constexpr (PATH && DROP) {
+      float dm[8];
+      drop_mult8(p.drop, m, n >> 3, dm);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = (v[k] + b[k]) * dm[k] * ps + r[k];
+    } else if constexpr (PATH) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = (v[k] + b[k]) * ps + r[k];
+    } else if constexpr (DROP) {
       float dm[8];
       drop_mult8(p.drop, m, n >> 3, dm);
 #pragma unroll
@@ -433,9 +456,10 @@ __device__ __forceinline__ void keep_live(const uint4& x) {
 // registers; v becomes the values written (col_partial sums them), o the packed store words
 template <int EPI>
 __device__ __forceinline__ void epi_prep8(const GemmDev& p, int m, int n, float* v, const float* pre, const float* b,
-                                          uint4* o) {
+                                          uint4* o, float ps = 1.0f) {
   constexpr int E = EPI & 15;
   constexpr bool DROP = (EPI & EPI_DROP) != 0;
+  constexpr bool PATH = (EPI & EPI_PATH) != 0;
   if constexpr (E == VIT_EPI_F32 || E == VIT_EPI_SPLITK) {
     if constexpr ((EPI & EPI_ACC) != 0) {
       // pre: the destination's old values (AuxPre). A select per value on the member's wave-uniform bit, no branch:
@@ -462,7 +486,15 @@ __device__ __forceinline__ void epi_prep8(const GemmDev& p, int m, int n, float*
     o[0] = pack8bf(v);
     o[1] = pack8bf(gl);
   } else if constexpr (E == VIT_EPI_BIAS_RESID_F32) {
-    if constexpr (DROP) {
+    if constexpr (PATH && DROP) {
+      float dm[8];
+      drop_mult8(p.drop, m, n >> 3, dm);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = (v[k] + b[k]) * dm[k] * ps + pre[k];
+    } else if constexpr (PATH) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = (v[k] + b[k]) * ps + pre[k];
+    } else if constexpr (DROP) {
       float dm[8];
       drop_mult8(p.drop, m, n >> 3, dm);
 #pragma unroll
@@ -598,17 +630,22 @@ __device__ __forceinline__ void epilogue_fast(const GemmDev& p, v4f (&acc)[8][FN
     if (p.bias) ld8f(p.bias + z * p.bias_bs + n, bv);
   }
   uint4 fc[ITF][AW], fn_[ITF][AW];
-  auto fetch_f = [&](uint4 (*ax)[AW], int pass) {
+  float pc[ITF], pn[ITF];  // EPI_PATH: the rows' stochastic-depth multipliers, requested with the aux chunks
+  auto fetch_f = [&](uint4 (*ax)[AW], float* px, int pass) {
     if constexpr (AuxPre<EPI>::W > 0) {
 #pragma unroll
       for (int it = 0; it < ITF; ++it) AuxPre<EPI>::fetch(p, mw0 + pass * PF + (lane + it * 64) / CPR, n, ax[it], z);
     }
+    if constexpr ((EPI & EPI_PATH) != 0) {
+#pragma unroll
+      for (int it = 0; it < ITF; ++it) px[it] = path_mult(p, mw0 + pass * PF + (lane + it * 64) / CPR);
+    }
   };
-  fetch_f(fc, 0);
+  fetch_f(fc, pc, 0);
   uint4 ob[NSET][ITF][W];
 #pragma unroll
   for (int pass = 0; pass < NPF; ++pass) {
-    if (pass + 1 < NPF) fetch_f(fn_, pass + 1);
+    if (pass + 1 < NPF) fetch_f(fn_, pn, pass + 1);
 #pragma unroll
     for (int jn = 0; jn < FN; ++jn)
 #pragma unroll
@@ -622,7 +659,10 @@ __device__ __forceinline__ void epilogue_fast(const GemmDev& p, v4f (&acc)[8][FN
       float v[8], u[8];
       ld8f(ws + row * LDW + ch * 8, v);
       if constexpr (AuxPre<EPI>::W > 0) AuxPre<EPI>::unpack(fc[it], u);
-      epi_prep8<EPI>(p, mw0 + pass * PF + row, n, v, u, bv, os[it]);
+      if constexpr ((EPI & EPI_PATH) != 0)
+        epi_prep8<EPI>(p, mw0 + pass * PF + row, n, v, u, bv, os[it], pc[it]);
+      else
+        epi_prep8<EPI>(p, mw0 + pass * PF + row, n, v, u, bv, os[it]);
       if (p.col_partial) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) csum[k] += v[k];
@@ -637,6 +677,10 @@ __device__ __forceinline__ void epilogue_fast(const GemmDev& p, v4f (&acc)[8][FN
       for (int it = 0; it < ITF; ++it)
 #pragma unroll
         for (int w = 0; w < AW; ++w) fc[it][w] = fn_[it][w];
+    }
+    if constexpr ((EPI & EPI_PATH) != 0) {
+#pragma unroll
+      for (int it = 0; it < ITF; ++it) pc[it] = pn[it];
     }
   }
 #pragma unroll
@@ -854,13 +898,21 @@ __global__ void __launch_bounds__(WM* WN * 64, (gemm_min_waves<BM, BN, BK, STAGE
         for (int it = 0; it < ITB; ++it)
           AuxPre<EPI>::fetch(p, m0 + pass * PASS_ROWS + (threadIdx.x + it * NT) / CPR, n, ax[it]);
       }
+      float psc[ITB];  // EPI_PATH: the rows' stochastic-depth multipliers, requested with the aux chunks
+      if constexpr ((EPI & EPI_PATH) != 0) {
+#pragma unroll
+        for (int it = 0; it < ITB; ++it) psc[it] = path_mult(p, m0 + pass * PASS_ROWS + (threadIdx.x + it * NT) / CPR);
+      }
 #pragma unroll
       for (int it = 0; it < ITB; ++it) {
         const int row = (threadIdx.x + it * NT) / CPR;
         float v[8], u[8];
         ld8f(cs + row * LDC + ch * 8, v);
         if constexpr (AuxPre<EPI>::W > 0) AuxPre<EPI>::unpack(ax[it], u);
-        epi_prep8<EPI>(p, m0 + pass * PASS_ROWS + row, n, v, u, bv, ob[it]);
+        if constexpr ((EPI & EPI_PATH) != 0)
+          epi_prep8<EPI>(p, m0 + pass * PASS_ROWS + row, n, v, u, bv, ob[it], psc[it]);
+        else
+          epi_prep8<EPI>(p, m0 + pass * PASS_ROWS + row, n, v, u, bv, ob[it]);
         if (p.col_partial) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) csum[k] += v[k];
@@ -881,6 +933,19 @@ __global__ void __launch_bounds__(WM* WN * 64, (gemm_min_waves<BM, BN, BK, STAGE
       if (m >= p.M || n >= p.N) continue;
       float v[8];
       ld8f(cs + row * LDC + ch * 8, v);
+      if constexpr ((EPI & EPI_PATH) != 0) {  // one multiplier load per row chunk, for either store path
+        const float ps = path_mult(p, m);
+        if (p.vec && n + 8 <= p.N) {
+          epi_store8<EPI>(p, z, split_idx, m, n, v, nullptr, ps);
+          if (p.col_partial) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) csum[k] += v[k];
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) epi_store<EPI>(p, z, split_idx, m, n + k, v[k], ps);
+        }
+      } else
       if (p.vec && n + 8 <= p.N) {
         epi_store8<EPI>(p, z, split_idx, m, n, v);  // v becomes the stored values
         if (p.col_partial) {
@@ -1190,6 +1255,19 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(const GemmDev p) {
       float v[8];
       ld8f(ws + row * LDW + ch * 8, v);
       if (m >= p.M || n >= p.N) continue;
+      if constexpr ((EPI & EPI_PATH) != 0) {  // one multiplier load per row chunk, for either store path
+        const float ps = path_mult(p, m);
+        if (p.vec && n + 8 <= p.N) {
+          epi_store8<EPI>(p, z, split_idx, m, n, v, nullptr, ps);
+          if (p.col_partial) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) csum[k] += v[k];
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) epi_store<EPI>(p, z, split_idx, m, n + k, v[k], ps);
+        }
+      } else
       if (p.vec && n + 8 <= p.N) {
         epi_store8<EPI>(p, z, split_idx, m, n, v);
         if (p.col_partial) {

@@ -397,6 +397,21 @@ __device__ __forceinline__ void pp2_tile(const GemmDev& p, const int tm, const i
       float v[8];
       ld8f(ws + row * LDW + ch * 8, v);
       if (m >= p.M || n >= p.N || p.diag == 1 || (p.diag == 3 && (blockIdx.x & 1))) continue;
+      if constexpr ((EPI & EPI_PATH) != 0) {  // stochastic depth (GW > 0: a BIAS_RESID_F32 variant): one multiplier
+        const float ps = path_mult(p, m);      // load per row chunk, for either store path
+        if (p.vec && n + 8 <= p.N) {
+          float u[8];
+          AuxPre<EPI>::unpack(axc[it], u);
+          epi_store8<EPI>(p, z, split_idx, m, n, v, u, ps);
+          if (p.col_partial) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) csum[k] += v[k];
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) epi_store<EPI>(p, z, split_idx, m, n + k, v[k], ps);
+        }
+      } else
       if (p.vec && n + 8 <= p.N) {
         if constexpr (GW > 0) {
           float u[8];

@@ -31,6 +31,11 @@ class Dropout(ctypes.Structure):
                 ("row_stride", c_i64)]
 
 
+class DropPath(ctypes.Structure):
+    """struct vit_drop_path (include/vit_hip.h)"""
+    _fields_ = [("scale", c_vp), ("rows_per_sample", c_i64)]
+
+
 class GemmArgs(ctypes.Structure):
     _fields_ = [
         ("M", c_i64), ("N", c_i64), ("K", c_i64),
@@ -174,6 +179,12 @@ _SIGS = {
     "vit_rows_select": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]),
     "vit_sgd_step_dev": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_f32, c_vp]),
     "vit_build_id": (ctypes.c_char_p, []),
+    "vit_drop_path_scales": (c_i32, [ctypes.POINTER(c_f32), c_i32, c_i64, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp]),
+    "vit_gemm_bf16_drop_path": (c_i32, [ctypes.POINTER(GemmArgs), ctypes.POINTER(DropPath), c_vp]),
+    "vit_layernorm_bwd_drop_path": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64,
+                                            c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, ctypes.POINTER(Dropout),
+                                            ctypes.POINTER(DropPath), c_vp]),
+    "vit_row_scale_f32": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -33,6 +33,9 @@ src/config.py:57-104). Additions for the MI355X path, all optional:
                          step (0: off); each epoch also validates the EMA weights (val_ema_*) and the checkpoint gains
                          "state_dict_ema"
   --use-ema              (eval) evaluate the checkpoint's "state_dict_ema"
+  --drop-path-rate R     (train) stochastic depth with timm's semantics (drop_path, scale_by_keep, linear depth rule):
+                         layer i of L drops each residual branch per sample with probability R i / (L - 1), fused into
+                         the residual GEMM epilogues; the cls-only last layer is off with it (0: off)
 
 Without --synthetic, the reference's own commands run on CIFAR read from disk (vitmi.datasets, vitmi.data):
     python -m vitmi.train --dataset CIFAR100 --num-classes 100 --data-dir ../data --checkpoint-path w.pth ...
@@ -167,10 +170,14 @@ def get_train_config(argv=None):
                         help="auto: onecycle for sgd, cosine (linear warm-up, cosine decay to 0) for adamw")
     parser.add_argument("--ema-decay", type=float, default=0.0,
                         help="keep an exponential moving average of the weights with this decay (0: off)")
+    parser.add_argument("--drop-path-rate", type=float, default=0.0,
+                        help="stochastic depth: the last layer's drop-path rate, linear from 0 over the layers (0: off)")
     config = parser.parse_args(argv)
     _check_image_size(config)
     check_augment_args(config)
     check_optimizer_args(config)
+    if not 0.0 <= config.drop_path_rate < 1.0:
+        raise SystemExit(f"--drop-path-rate {config.drop_path_rate:g}: expected a value in [0, 1) (0: off)")
     if config.accum_steps < 1 or config.batch_size % (config.accum_steps * max(1, config.n_gpu)):
         raise SystemExit(f"--batch-size {config.batch_size} is the batch of one optimizer step and must divide evenly "
                          f"into --accum-steps {config.accum_steps} micro-batches on each of {config.n_gpu} GPUs")

@@ -205,6 +205,9 @@ class _Acts:
         self.dlncls = z(b, D, dt=f)
         self.dlogits = z(b, cfg.num_classes, dt=f)
         self.row_stats = z(b, 3, dt=f)
+        # stochastic depth: per-sample multipliers of the 2L residual branches of the last training forward
+        # (site 2i = attention, 2i + 1 = MLP of layer i; ops.drop_path_scales), read again by the backward
+        self.path_scale = z(2 * L, b, dt=f)
         # bias-gradient partial sums, reduced a layer at a time (_BiasReducer: one vit_colsum_batch launch)
         self.lnparts = [z(ops.layernorm_bwd_blocks(T), 3 * D, dt=f) for _ in range(_NBUF)]
         self.gelu_parts = [z(-(-T // 128), M, dt=f) for _ in range(_NBUF)]  # per-M-tile column sums of dU (fc1 bias)
@@ -420,7 +423,8 @@ class ViTEngine:
         # so that layer's out-projection, LayerNorm 2 and MLP (forward and backward) run on the b cls
         # rows and its attention on the first 32-query pair of each (image, head) (q_rows = 1); the
         # q|k|v projection stays full (every token is a key / value of the cls query). Same logits, loss and gradients (zero rows add exact zeros); VITMI_PRUNE_LAST=0
-        # runs every token. Off while dropout is active.
+        # runs every token. Off while dropout or drop-path (stochastic depth) is active: both index masks by the full
+        # token rows.
         self.prune_last = os.environ.get("VITMI_PRUNE_LAST", "1") != "0"
         self._pruned = False
         self._side = None
@@ -433,6 +437,9 @@ class ViTEngine:
         self.drop_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & (2**64 - 1)
         self._drop_offset = 0
         self._drop = None  # (p, seed, offset) of the last forward, or None
+        # stochastic depth (timm drop_path, scale_by_keep, linear depth rule): per-site rates of the last forward, or
+        # None. The draw is the dropout scheme's (seed, offset) at sites 0x80000000 | s
+        self._path = None
 
     def _event(self):
         """the next event of the backward's pool (created once, re-recorded every step: a wait enqueued
@@ -508,10 +515,19 @@ class ViTEngine:
         p, seed, off = self._drop
         return ops.dropout_desc(p, site, seed, off, row_stride)
 
-    def forward(self, x: torch.Tensor, dropout_p: float = 0.0):
+    def _pp(self, a, site, rows_per_sample):
+        """drop-path descriptor of branch `site` for the last forward (None when its rate is 0: the plain kernels)"""
+        if self._path is None or site < 0 or not self._path[site] > 0.0:
+            return None
+        return ops.drop_path_desc(a.path_scale[site], rows_per_sample)
+
+    def forward(self, x: torch.Tensor, dropout_p: float = 0.0, drop_path_rate: float = 0.0):
         """x: [b, 3, img, img] fp32 on the device. Returns logits [b, C] (fp32, engine-owned).
         dropout_p > 0: training-mode nn.Dropout(p) at the reference's four sites per model
-        (position embedding; per layer the attention output, GELU output and fc2 output)."""
+        (position embedding; per layer the attention output, GELU output and fc2 output).
+        drop_path_rate > 0: training-mode stochastic depth on both residual branches of layer i at rate
+        drop_path_rate * i / (L - 1), one multiplier per sample (0 or 1 / (1 - p_i)) on the branch after its dropout,
+        fused into the two residual GEMM epilogues."""
         cfg = self.cfg
         if x.dim() != 4 or x.shape[1] != 3 or tuple(x.shape[2:]) != cfg.image_hw:
             raise ValueError(f"expected input [b, 3, {cfg.image_hw[0]}, {cfg.image_hw[1]}], got {tuple(x.shape)}")
@@ -523,13 +539,25 @@ class ViTEngine:
         T = a.T
         mv = self.mirror
         f = self.flat
-        if dropout_p and dropout_p > 0.0:
-            if not dropout_p < 1.0:
-                raise ValueError(f"dropout probability has to be in [0, 1), got {dropout_p}")
-            self._drop_offset += 1
-            self._drop = (float(dropout_p), self.drop_seed, self._drop_offset)
+        use_drop = bool(dropout_p and dropout_p > 0.0)
+        # (a single layer has rate 0 at both sites, the linear rule's first point: nothing to draw, the plain step)
+        use_path = bool(drop_path_rate and drop_path_rate > 0.0) and L > 1
+        if use_drop and not dropout_p < 1.0:
+            raise ValueError(f"dropout probability has to be in [0, 1), got {dropout_p}")
+        if drop_path_rate and not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop-path rate has to be in [0, 1), got {drop_path_rate}")
+        if use_path and 2 * L > ops.DROP_PATH_MAX_SITES:
+            raise NotImplementedError(f"drop-path: {L} layers need {2 * L} branch sites, the table launch takes "
+                                      f"{ops.DROP_PATH_MAX_SITES} (VIT_DROP_PATH_MAX_SITES)")
+        if use_drop or use_path:
+            self._drop_offset += 1  # one (seed, offset) per forward for both draws
+        self._drop = (float(dropout_p), self.drop_seed, self._drop_offset) if use_drop else None
+        if use_path:
+            rates = [float(drop_path_rate) * i / (L - 1) for i in range(L)]
+            self._path = [r for r in rates for _ in range(2)]
+            ops.drop_path_scales(self._path, b, self.drop_seed, self._drop_offset, a.path_scale)
         else:
-            self._drop = None
+            self._path = None
         dd = self._dd
         # patch embedding: im2col + GEMM with conv-bias / cls / pos-emb epilogue
         ops.im2col_hw(x, a.patches, b, *cfg.image_hw, *cfg.patch_hw, a.kpad)
@@ -539,7 +567,7 @@ class ViTEngine:
                  aux=f[self.off("transformer.pos_embedding.pos_embedding"):], ldaux=D,
                  aux2=f[self.off("cls_token"):], tokens=N, dropout=dd(0))
         scale = 1.0 / math.sqrt(hd)
-        self._pruned = self.prune_last and self._drop is None
+        self._pruned = self.prune_last and self._drop is None and self._path is None
         for i in range(L):
             ln = lambda s: self.off(self.lname(i, s))
             ops.layernorm_fwd(a.h[i], D, f[ln("norm1.weight"):], f[ln("norm1.bias"):], a.ln1[i], D, a.mu1[i],
@@ -554,7 +582,7 @@ class ViTEngine:
                 break
             ops.gemm(a.o[i], mv[ln("attn.out.weight"):], a.hm[i], T, D, D, a_layout=K_CONTIG, b_layout=MN_CONTIG,
                      lda=D, ldb=D, ldc=D, epilogue=EPI_BIAS_RESID_F32, bias=f[ln("attn.out.bias"):], aux=a.h[i],
-                     ldaux=D, dropout=dd(1 + 3 * i))
+                     ldaux=D, dropout=dd(1 + 3 * i), drop_path=self._pp(a, 2 * i, N))
             ops.layernorm_fwd(a.hm[i], D, f[ln("norm2.weight"):], f[ln("norm2.bias"):], a.ln2[i], D, a.mu2[i],
                               a.rs2[i], T, D)
             wgrad.timed(self.probe, (), ops.gemm, a.ln2[i], mv[ln("mlp.fc1.weight"):], a.gp[i], T, M, D,
@@ -562,7 +590,7 @@ class ViTEngine:
                         bias=f[ln("mlp.fc1.bias"):], C2=a.g[i], ldc2=M, dropout=dd(2 + 3 * i))
             ops.gemm(a.g[i], mv[ln("mlp.fc2.weight"):], a.h[i + 1], T, D, M, a_layout=K_CONTIG, b_layout=K_CONTIG,
                      lda=M, ldb=M, ldc=D, epilogue=EPI_BIAS_RESID_F32, bias=f[ln("mlp.fc2.bias"):], aux=a.hm[i],
-                     ldaux=D, dropout=dd(3 + 3 * i))
+                     ldaux=D, dropout=dd(3 + 3 * i), drop_path=self._pp(a, 2 * i + 1, N))
         # final LayerNorm on the cls rows only (only row 0 reaches the classifier, src/model.py:210)
         ops.layernorm_fwd(a.h[L], N * D, f[self.off("transformer.norm.weight"):], f[self.off("transformer.norm.bias"):],
                           a.lncls, D, a.muf, a.rsf, b, D)
@@ -775,7 +803,9 @@ class ViTEngine:
         bias.ln_bwd(a.dlncls, D, a.h[L], N * D, a.muf, a.rsf, f[self.off("transformer.norm.weight"):], a.dh, N * D, b,
                     gv("transformer.norm.weight"), gv(self.lname(L - 1, "mlp.fc2.bias")),
                     dx_bf16=a.c_dh if pruned else dhbs[wb], lddxb=D if pruned else N * D,
-                    dx_dropout=dd(3 + 3 * (L - 1), N))
+                    dx_dropout=dd(3 + 3 * (L - 1), N),
+                    # (cls rows: mask row = row * N with dropout's descriptor, the row itself without it)
+                    dx_path=self._pp(a, 2 * (L - 1) + 1, N if self._drop is not None else 1))
         fire(self.layout.buckets[0])
         scale = 1.0 / math.sqrt(hd)
         for i in reversed(range(L)):
@@ -809,7 +839,8 @@ class ViTEngine:
                 dhb = dhbs[wb]
                 bias.ln_bwd(a.dyln, D, a.hm[i], D, a.mu2[i], a.rs2[i], f[ln("norm2.weight"):], a.dh, D, T,
                             gv(self.lname(i, "norm2.weight")), gv(self.lname(i, "attn.out.bias")),
-                            dres=a.dh, lddres=D, dx_bf16=dhb, lddxb=D, dx_dropout=dd(1 + 3 * i))
+                            dres=a.dh, lddres=D, dx_bf16=dhb, lddxb=D, dx_dropout=dd(1 + 3 * i),
+                            dx_path=self._pp(a, 2 * i, N))
                 # ---- attention: hm = h + out(attn(ln1(h))) ----
                 # (grouped: launched with the q|k|v weight gradient below, dhb stays intact until then)
                 wq.push(Spec(a.o[i], D, dhb, D, D, D, gv(self.lname(i, "attn.out.weight")), D),
@@ -837,7 +868,8 @@ class ViTEngine:
             bias.ln_bwd(a.dyln, D, a.h[i], D, a.mu1[i], a.rs1[i], f[ln("norm1.weight"):], a.dh, D, T,
                         gv(self.lname(i, "norm1.weight")), gv(self.lname(i - 1, "mlp.fc2.bias")) if i > 0 else None,
                         dres=a.dh, lddres=D, dx_bf16=dhbs[wb], lddxb=D,
-                        dx_dropout=dd(3 + 3 * (i - 1)) if i > 0 else dd(0))
+                        dx_dropout=dd(3 + 3 * (i - 1)) if i > 0 else dd(0),
+                        dx_path=self._pp(a, 2 * (i - 1) + 1, N))
             fire(self.layout.buckets[L - i])
         # ---- embedding: conv weight grad (wgrad over patches), bias / pos / cls ----
         wq.push(Spec(dhbs[wb], D, a.patches, a.kpad, D, cfg.patch_k, gv("embedding.weight"), cfg.patch_k))

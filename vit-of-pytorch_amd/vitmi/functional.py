@@ -286,6 +286,44 @@ def dropout(x, p, training):
     return HipDropout.apply(x, float(p))
 
 
+class HipDropPath(torch.autograd.Function):
+    """x [b, n, D] times one multiplier per sample (ops.drop_path_scales at the standalone path's own site); the
+    backward scales the gradient by the same table."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        x = _f32(x)
+        b, rps, cols = x.shape[0], x.shape[1], x.shape[2]
+        d = _drop_desc(p, cols)  # the standalone path's own seed; advances its offset
+        scale = torch.empty(1, b, device=x.device, dtype=torch.float32)
+        ops.drop_path_scales([p], b, d.seed, d.offset, scale)  # branch site 0 of that stream
+        y = torch.empty_like(x)
+        ops.row_scale_f32(x, y, b * rps, cols, scale, rps)
+        ctx.scale, ctx.dims = scale, (b * rps, cols, rps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _f32(dy)
+        dx = torch.empty_like(dy)
+        rows, cols, rps = ctx.dims
+        ops.row_scale_f32(dy, dx, rows, cols, ctx.scale, rps)
+        return dx, None
+
+
+def drop_path(x, p, training):
+    """Stochastic depth (timm.layers.drop_path, scale_by_keep=True) on x [b, n, D]: each sample's branch is zeroed
+    with probability p, else scaled by 1 / (1 - p); identity in eval mode or at p = 0."""
+    if not training or p == 0.0:
+        return x
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"drop-path probability has to be in [0, 1), got {p}")
+    if x.dim() != 3:
+        raise ValueError(f"drop_path expects [b, n, D], got {tuple(x.shape)}")
+    _gpu(x)
+    return HipDropPath.apply(x, float(p))
+
+
 class HipAdd(torch.autograd.Function):
     """out = x + y, y broadcast over x's leading dims (y.numel() divides x.numel())."""
 

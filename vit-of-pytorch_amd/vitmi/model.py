@@ -25,7 +25,7 @@ from . import functional as HF
 from .engine import ArchConfig, ViTEngine
 
 __all__ = ["PositionEmbs", "MlpBlock", "MLPBlock", "LinearGeneral", "SelfAttention", "EncoderBlock", "Encoder",
-           "VisionTransformer", "CrossEntropyLoss", "Linear", "LayerNorm", "GELU", "Dropout"]
+           "VisionTransformer", "CrossEntropyLoss", "Linear", "LayerNorm", "GELU", "Dropout", "DropPath"]
 
 
 # ---- torch.nn leaves on the HIP kernels (same constructors, parameters and RNG draws) --------------
@@ -59,6 +59,20 @@ class Dropout(nn.Dropout):
 
     def forward(self, x):
         return HF.dropout(x, self.p, self.training)
+
+
+class DropPath(nn.Module):
+    """Stochastic depth per sample (timm.layers.DropPath, scale_by_keep=True) on a residual branch [b, n, D]."""
+
+    def __init__(self, drop_prob=0.0):
+        super().__init__()
+        self.drop_prob = float(drop_prob)
+
+    def forward(self, x):
+        return HF.drop_path(x, self.drop_prob, self.training)
+
+    def extra_repr(self):
+        return f"drop_prob={self.drop_prob:0.3f}"
 
 
 class PositionEmbs(nn.Module):
@@ -143,8 +157,11 @@ class SelfAttention(nn.Module):
 class EncoderBlock(nn.Module):
     """reference src/model.py:104-130 (pre-LN)."""
 
-    def __init__(self, in_dim, mlp_dim, num_heads, dropout_rate=0.1, attn_dropout_rate=0.1):
+    def __init__(self, in_dim, mlp_dim, num_heads, dropout_rate=0.1, attn_dropout_rate=0.1, drop_path_rate=0.0):
         super().__init__()
+        if not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate has to be in [0, 1), got {drop_path_rate}")
+        self.drop_path_rate = float(drop_path_rate)  # (a plain attribute: no module, the state_dict keeps its keys)
         self.norm1 = LayerNorm(in_dim)
         self.attn = SelfAttention(in_dim, heads=num_heads, dropout_rate=attn_dropout_rate)
         self.dropout = Dropout(dropout_rate) if dropout_rate > 0 else None
@@ -157,23 +174,35 @@ class EncoderBlock(nn.Module):
         out = self.attn(out)
         if self.dropout:
             out = self.dropout(out)
+        out = HF.drop_path(out, self.drop_path_rate, self.training)
         out = HF.add(out, residual)
         residual = out
         out = self.norm2(out)
         out = self.mlp(out)
+        out = HF.drop_path(out, self.drop_path_rate, self.training)
         return HF.add(out, residual)
+
+
+def drop_path_rates(rate, num_layers):
+    """timm's linear depth rule: layer i of L drops its branches with probability rate * i / (L - 1)
+    (torch.linspace(0, rate, L)); 0 for a single layer."""
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop_path_rate has to be in [0, 1), got {rate}")
+    return [float(rate) * i / (num_layers - 1) if num_layers > 1 else 0.0 for i in range(num_layers)]
 
 
 class Encoder(nn.Module):
     """reference src/model.py:133-156"""
 
     def __init__(self, num_patches, emb_dim, mlp_dim, num_layers=12, num_heads=12, dropout_rate=0.1,
-                 attn_dropout_rate=0.0):
+                 attn_dropout_rate=0.0, drop_path_rate=0.0):
         super().__init__()
         self.pos_embedding = PositionEmbs(num_patches, emb_dim, dropout_rate)
         self.encoder_layers = nn.ModuleList()
-        for _ in range(num_layers):
-            self.encoder_layers.append(EncoderBlock(emb_dim, mlp_dim, num_heads, dropout_rate, attn_dropout_rate))
+        self.drop_path_rates = drop_path_rates(drop_path_rate, num_layers)
+        for i in range(num_layers):
+            self.encoder_layers.append(EncoderBlock(emb_dim, mlp_dim, num_heads, dropout_rate, attn_dropout_rate,
+                                                    drop_path_rate=self.drop_path_rates[i]))
         self.norm = LayerNorm(emb_dim)
 
     def forward(self, x):
@@ -189,7 +218,8 @@ class _ViTFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, *params):
         eng = model._engine
-        logits = eng.forward(x, dropout_p=model.dropout_rate if model.training else 0.0)
+        logits = eng.forward(x, dropout_p=model.dropout_rate if model.training else 0.0,
+                             drop_path_rate=model.drop_path_rate if model.training else 0.0)
         ctx.model = model
         ctx.step = eng.step_id
         return logits.clone()
@@ -229,7 +259,8 @@ class VisionTransformer(nn.Module):
     """reference src/model.py:159-211 — same ctor, state_dict and forward contract."""
 
     def __init__(self, image_size=(256, 256), patch_size=(16, 16), emb_dim=768, mlp_dim=3072, num_heads=12,
-                 num_layers=12, num_classes=1000, attn_dropout_rate=0.0, dropout_rate=0.1, feat_dim=None):
+                 num_layers=12, num_classes=1000, attn_dropout_rate=0.0, dropout_rate=0.1, feat_dim=None,
+                 drop_path_rate=0.0):
         super().__init__()
         h, w = image_size
         fh, fw = patch_size
@@ -239,7 +270,7 @@ class VisionTransformer(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, emb_dim))
         self.transformer = Encoder(num_patches=num_patches, emb_dim=emb_dim, mlp_dim=mlp_dim, num_layers=num_layers,
                                    num_heads=num_heads, dropout_rate=dropout_rate,
-                                   attn_dropout_rate=attn_dropout_rate)
+                                   attn_dropout_rate=attn_dropout_rate, drop_path_rate=drop_path_rate)
         self.classifier = Linear(emb_dim, num_classes)
         square = h == w and fh == fw  # square models keep the int configs they always built
         self.arch = ArchConfig(image_size=h if square else (h, w), patch_size=fh if square else (fh, fw),
@@ -247,6 +278,10 @@ class VisionTransformer(nn.Module):
                                num_layers=num_layers, num_classes=num_classes)
         self.dropout_rate = dropout_rate
         self.attn_dropout_rate = attn_dropout_rate
+        self.drop_path_rate = float(drop_path_rate)  # stochastic depth, training mode only (ViTEngine.forward)
+        if drop_path_rate > 0 and num_layers > 1 and 2 * num_layers > 128:  # VIT_DROP_PATH_MAX_SITES
+            raise NotImplementedError(f"drop_path_rate: {num_layers} layers need {2 * num_layers} branch sites, the "
+                                      "engine's table launch takes 128")
         # "bf16": the training path (bf16 MFMA operands, fp32 accumulation, autograd through the HIP
         # engine). "fp32": forward-only in the reference's own arithmetic (f32 operands everywhere),
         # for the logits-parity gate and fp32 evaluation; its output carries no autograd graph.
@@ -351,9 +386,9 @@ class VisionTransformer(nn.Module):
         # (attn_dropout_rate builds SelfAttention.dropout, which the reference never applies: src/model.py:78-99)
         eng = self.engine()
         if self.precision == "fp32":
-            if self.training and self.dropout_rate > 0:
-                raise NotImplementedError("precision='fp32' is the forward-only exact path; train-mode dropout runs on "
-                                          "the bf16 path (use model.eval() for fp32 evaluation)")
+            if self.training and (self.dropout_rate > 0 or self.drop_path_rate > 0):
+                raise NotImplementedError("precision='fp32' is the forward-only exact path; train-mode dropout and "
+                                          "drop-path run on the bf16 path (use model.eval() for fp32 evaluation)")
             if torch.is_grad_enabled() and any(p.requires_grad for p in self._flat_params):
                 raise RuntimeError("precision='fp32' is the forward-only exact path; run it under torch.no_grad() "
                                    "(training uses precision='bf16')")

@@ -11,7 +11,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import COLSUM_BATCH_MAX, Dropout, GemmArgs, check
+from ._lib import COLSUM_BATCH_MAX, DropPath, Dropout, GemmArgs, check
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -75,6 +75,56 @@ def dropout_mask(d, row0, rows, cols, out, ld):
     check(lib().vit_dropout_mask(_dp(d), row0, rows, cols, _p(out), ld, _stream()), "vit_dropout_mask")
 
 
+DROP_PATH_SITE = 0x80000000  # dropout site of branch site s: DROP_PATH_SITE | s (vit_drop_path_scales)
+DROP_PATH_MAX_SITES = 128  # VIT_DROP_PATH_MAX_SITES
+
+
+def drop_path_desc(scale, rows_per_sample):
+    """struct vit_drop_path: scale f32 [samples] (a row of drop_path_scales' table), sample of row r = r // rows_per_sample"""
+    _chk(scale, F32, "scale")
+    d = DropPath(scale.data_ptr(), int(rows_per_sample))
+    d._keep = scale  # the table row outlives the descriptor's launches
+    return d
+
+
+def drop_path_scales(p_site, B, seed, offset, out):
+    """out[s, b] = stochastic-depth multiplier (0 or 1/(1-p_site[s])) of sample b at branch site s: the dropout
+    multiplier of element (b, 0) of dropout site DROP_PATH_SITE | s under (seed, offset). One launch, no sync."""
+    _chk(out, F32, "out")
+    n = len(p_site)
+    if out.numel() < n * B or not out.is_contiguous():
+        raise ValueError("drop_path_scales: out must be a contiguous f32 [len(p_site), B]")
+    arr = (ctypes.c_float * n)(*[float(p) for p in p_site])
+    check(lib().vit_drop_path_scales(arr, n, B, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _p(out), _stream()),
+          "vit_drop_path_scales")
+
+
+def row_scale_f32(inp, out, rows, cols, scale, rows_per_sample):
+    """out[r, c] = inp[r, c] * scale[r // rows_per_sample] (in place allowed)"""
+    _chk(inp, F32, "inp")
+    _chk(out, F32, "out")
+    _chk(scale, F32, "scale")
+    check(lib().vit_row_scale_f32(_p(inp), _p(out), rows, cols, _p(scale), rows_per_sample, _stream()),
+          "vit_row_scale_f32")
+
+
+def gemm_drop_path(A, B, C, M, N, K, drop_path=None, **kw):
+    """vit_gemm_bf16_drop_path: the BIAS_RESID_F32 GEMM whose branch is multiplied per sample (drop_path_desc) before
+    the residual add; drop_path None is exactly gemm(...)"""
+    _chk(A, BF16, "A")
+    _chk(B, BF16, "B")
+    a = _gemm_args(A, B, C, M, N, K, **kw)
+    probe = GEMM_PROBE is not None and M >= GEMM_PROBE_MIN_M  # (as gemm(): the roofline probe sees these GEMMs too)
+    if probe:
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    check(lib().vit_gemm_bf16_drop_path(ctypes.byref(a), _dp(drop_path), _stream()), "vit_gemm_bf16_drop_path")
+    if probe:
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev1.record()
+        GEMM_PROBE.append((ev0, ev1, 2.0 * M * N * K * a.batch, int(a.epilogue)))
+
+
 # bench.py's roofline_fwd_dgrad probe: when a list, every vit_gemm_bf16 call with M >= GEMM_PROBE_MIN_M
 # that is not a split-K weight gradient appends (start event, end event, 2 M N K, epilogue), the events recorded
 # on the stream the call runs on (one call = the 256x256 kernel and its wave-split remainder launch)
@@ -82,9 +132,14 @@ GEMM_PROBE = None
 GEMM_PROBE_MIN_M = 0
 
 
-def gemm(A, B, C, M, N, K, part=0, **kw):
+def gemm(A, B, C, M, N, K, part=0, drop_path=None, **kw):
     """bf16 MFMA GEMM, C[m,n] = sum_k A(m,k) B(k,n) + fused epilogue (see vit_gemm_args).
-    part 1 / 2: only the whole-wave rows / the wave-split remainder rows (vit_gemm_bf16_part)."""
+    part 1 / 2: only the whole-wave rows / the wave-split remainder rows (vit_gemm_bf16_part).
+    drop_path (drop_path_desc): the stochastic-depth variant of the BIAS_RESID_F32 epilogue (gemm_drop_path)."""
+    if drop_path is not None:
+        if part:
+            raise ValueError("gemm: drop_path has no part launches")
+        return gemm_drop_path(A, B, C, M, N, K, drop_path, **kw)
     _chk(A, BF16, "A")
     _chk(B, BF16, "B")
     a = _gemm_args(A, B, C, M, N, K, **kw)
@@ -152,7 +207,17 @@ def layernorm_bwd_blocks(rows):
 
 
 def layernorm_bwd(dy, lddy, x, ldx, mean, rstd, gamma, dx, lddx, partial, rows, D, *, dres=None, lddres=0,
-                  dx_bf16=None, lddxb=0, dgamma_dbeta=None, dx_colsum=None, accumulate=False, dx_dropout=None):
+                  dx_bf16=None, lddxb=0, dgamma_dbeta=None, dx_colsum=None, accumulate=False, dx_dropout=None,
+                  dx_path=None):
+    """dx_path (drop_path_desc): the bf16 copy and the dx column sums also carry the per-sample stochastic-depth
+    multiplier (vit_layernorm_bwd_drop_path); None is the plain entry"""
+    if dx_path is not None:
+        check(lib().vit_layernorm_bwd_drop_path(_p(dy), lddy, int(dy.dtype == F32), _p(x), ldx, _p(mean), _p(rstd),
+                                                _p(gamma), _p(dres), lddres, _p(dx), lddx, _p(dx_bf16), lddxb,
+                                                _p(partial), _p(dgamma_dbeta), _p(dx_colsum), int(accumulate), rows, D,
+                                                _dp(dx_dropout), _dp(dx_path), _stream()),
+              "vit_layernorm_bwd_drop_path")
+        return
     check(lib().vit_layernorm_bwd(_p(dy), lddy, int(dy.dtype == F32), _p(x), ldx, _p(mean), _p(rstd), _p(gamma),
                                   _p(dres), lddres, _p(dx), lddx, _p(dx_bf16), lddxb, _p(partial), _p(dgamma_dbeta),
                                   _p(dx_colsum), int(accumulate), rows, D, _dp(dx_dropout), _stream()),

@@ -396,7 +396,8 @@ def build_model(config, device):
                              patch_size=(config.patch_size, config.patch_size), emb_dim=config.emb_dim,
                              mlp_dim=config.mlp_dim, num_heads=config.num_heads, num_layers=config.num_layers,
                              num_classes=config.num_classes, attn_dropout_rate=config.attn_dropout_rate,
-                             dropout_rate=config.dropout_rate)
+                             dropout_rate=config.dropout_rate,
+                             drop_path_rate=getattr(config, "drop_path_rate", 0.0))
 
 
 def _launched_world(config):
